@@ -26,8 +26,19 @@ it does not shard: --gpus N runs N independent replicas (weak scaling).
 
 Output: one JSON line.  value = ciphertext-mults/s (relinearised ct x ct
 products, incl. those in the Chebyshev PS, summed over ranks / wall time);
-ms_per_step = sort wall time.  Also: roofline of the dominant kernel (HIP
-events on the engine stream) and the CPU-oracle baseline (rank 0, every world size).
+ms_per_step = sort wall time.  A plain run sets up, warms up, times --steps
+sorts and prints that line.
+
+--full adds what takes runs of its own: the roofline of the dominant kernel
+(one more sort under HIP events on the engine stream), the CPU-oracle baseline
+(rank 0, every world size) and, for DirectSort, --mask-steps sorts that
+re-encode every mask.  Without it those fields are null or absent.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+sort returned as DIR/<name>.npy (float64): the output ciphertext's RNS words
+(ct_words_lo / ct_words_hi: low and high 32 bits of each u64 word, shape
+(2, limbs, ringDim)) and its decryption (sorted).  Keys, encryption and input
+come from --seed, so two runs with the same arguments write the same arrays.
 """
 import argparse
 import json
@@ -70,21 +81,33 @@ def parse():
                     help="Paterson-Stockmeyer split: OpenFHE's (the reference's EvalChebyshevSeriesPS; holds the "
                          "0.01 bound at 40 bits) or rounds 1-2's power-of-two split (needs 50 bits at N=1024), "
                          "DESIGN.md §3")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true', help='skip the instrumented roofline sort (PMC passes)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the roofline sort, the CPU-oracle '
+                         'baseline and the --mask-steps sorts (each can still be switched off below)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the last timed sort\'s output ciphertext words and its '
+                         'decryption to DIR/<name>.npy (float64; rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU-oracle baseline')
+    ap.add_argument('--no-roofline', action='store_true',
+                    help='with --full: skip the instrumented roofline sort (PMC passes)')
     ap.add_argument('--cpu-sample-mults', type=int, default=0, help='override CPU sample size')
-    ap.add_argument('--clock-json', default=None, help='write the full per-kernel clock of the roofline sort here')
+    ap.add_argument('--clock-json', default=None,
+                    help='with --full: write the full per-kernel clock of the roofline sort here')
     ap.add_argument('--dnum', type=int, default=0, help='MEHP24: key-switch digits (0: the parameter table, OpenFHE default 3)')
     ap.add_argument('--lanes', type=int, default=2,
                     help='concurrent batch lanes (forked engines) per GPU (round 4, batched rotations: 2 lanes 589.6 ms, '
                          '3 lanes 604.0, 4 lanes 611.9, 1 lane 613.8; profiles/r4_lanes)')
     ap.add_argument('--stack', type=int, default=32, help='max batches stacked into one ciphertext batch')
     ap.add_argument('--mask-steps', type=int, default=2,
-                    help='extra sorts timed with every mask re-encoded per sort (0: skip)')
+                    help='with --full: extra sorts timed with every mask re-encoded per sort (0: skip)')
     ap.add_argument('--rendezvous-check', action='store_true',
                     help='launch/rendezvous only: ranks meet over gloo, exchange a max and a sum, rank 0 prints '
                          'one JSON line (no GPU work; the multi-rank launcher test)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:  # a plain run: set up, warm up, time the steps, print
+        a.no_roofline = a.no_cpu_baseline = True
+        a.mask_steps = 0
+    return a
 
 
 def launched_by_torchrun():
@@ -262,6 +285,25 @@ def device_sync(ctx):
             torch.cuda.synchronize()
     except Exception:
         pass
+
+
+DUMP_MAX_WORDS = 3 << 20  # x 2 float64 files = 48 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(dirname, out, y):
+    """--dump-outputs: the ciphertext the last timed sort returned, and its
+    decryption y.  The u64 RNS words ((2, limbs, ringDim), exact integers below
+    2^60) go out as two float64 arrays, low and high 32 bits, so nothing is
+    rounded; an output above DUMP_MAX_WORDS words (a k-way output high in the
+    modulus chain) is cut to a fixed seeded sample of its flattened words."""
+    os.makedirs(dirname, exist_ok=True)
+    w = out.data()
+    if w.size > DUMP_MAX_WORDS:
+        pick = np.sort(np.random.default_rng(0).choice(w.size, DUMP_MAX_WORDS, replace=False))
+        w = w.reshape(-1)[pick]
+    np.save(os.path.join(dirname, 'ct_words_lo.npy'), (w & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(dirname, 'ct_words_hi.npy'), (w >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(dirname, 'sorted.npy'), np.asarray(y, dtype=np.float64))
 
 
 _LIB_SHA = None
@@ -638,6 +680,8 @@ def run_mehp24(a, d):
     op_total = d.sum(cnt['opbytes'])
     if d.rank == 0:
         y = ctx.decrypt(out)[:N]
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out, y)
         ms = dt / a.steps * 1e3
         P = N // p['sub'] if p['sub'] else 1
         res = {
@@ -765,6 +809,8 @@ def run_kway(a, d):
     y = ctx.decrypt(out)[:N]
     err = d.max(float(np.max(np.abs(y - np.sort(x)))))
     if d.rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out, y)
         ms = dt / a.steps * 1e3
         res = {
             'metric': f'k-way encrypted sort seconds + ciphertext-mults/sec, k={k}, N={N} @ ringDim 2^{logN}',
@@ -899,6 +945,8 @@ def main():
     res = None
     if d.rank == 0:
         y = ctx.decrypt(out)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out, y)
         max_err = float(np.max(np.abs(y - np.sort(x))))
         ms = dt / a.steps * 1e3
         res = {

@@ -38,7 +38,7 @@ python scripts/pmc_sq_summary.py $O/pmc_sq/run_counter_collection.csv $O/pmc_sq$
 gzip -f $O/pmc_*/run_counter_collection.csv
 cp $O/pmc_traffic${PMCSFX}.json $O/pmc_sq${PMCSFX}.json profiles/
 unset FHE_PROF_REGION ROC_AQL_QUEUE_SIZE
-timeout -k 10 600 python bench.py "$@" > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -5 $O/bench.err; exit 1; }
 python - "$O/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d['roofline'] or {}

@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_mfma.py tests/test_gpu_dige
 tail -2 $O/tests.log
 for arm in pipe old pipe old; do
   case $arm in pipe) L="";; old) L="$R/fhe-sorting_amd/lib/ab_lffpipe0.so";; esac
-  FHE_LIB=$L timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$arm.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
+  FHE_LIB=$L timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$arm.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
   python -c "
 import json; d=json.load(open('$O/bench_$arm.json')); k=d['roofline']['kernels']
 print('$arm', d['ms_per_step'], d.get('max_abs_err'), {n: v['avg_us'] for n, v in k.items() if 'leaf' in n})"

@@ -11,7 +11,7 @@ FHE_KS_FUSE_INT=1 timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py
 tail -2 $O/tests.log
 for arm in int1 def int1 def; do
   case $arm in int1) E="FHE_KS_FUSE_INT=1";; def) E="FHE_KS_FUSE_INT=0";; esac
-  env $E timeout -k 10 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$arm.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
+  env $E timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_$arm.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
   python -c "
 import json; d=json.load(open('$O/bench_$arm.json')); r=d['roofline']; k=r['kernels']
 print('$arm', d['ms_per_step'], d.get('max_abs_err'), 'rank', r['phases']['rank_batches']['ms'], r['phases']['rank_batches']['kernel_over_op_bytes'], 'index', r['phases']['index_batches']['ms'])

@@ -14,7 +14,7 @@ for v in 0 1 0 1 0 1; do
   python -c "import json,sys; d=json.load(open('$O/bench_$v.json')); print('sort six=$v', d['ms_per_step'], d.get('max_abs_err'))" | tee -a $O/ab.txt
 done
 for v in 0 1; do
-  FHE_LEAF_SIX=$v timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/roof_$v.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
+  FHE_LEAF_SIX=$v timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/roof_$v.json 2>> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 1; }
   python -c "
 import json; d=json.load(open('$O/roof_$v.json')); r=d['roofline']
 for k,v in sorted(r['kernels'].items()):

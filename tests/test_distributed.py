@@ -218,6 +218,55 @@ def _bench_module():
     return m
 
 
+def test_bench_plain_run_leaves_the_side_measurements_to_full(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its K sorts and
+    nothing else: the roofline sort, the CPU-oracle baseline and the per-sort
+    mask-encoding sorts run only with --full, where their own switches still
+    hold."""
+    import sys
+    m = _bench_module()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '3'])
+    a = m.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert a.no_roofline and a.no_cpu_baseline and a.mask_steps == 0
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'd'])
+    a = m.parse()
+    assert a.full and a.dump_outputs == 'd'
+    assert not a.no_roofline and not a.no_cpu_baseline and a.mask_steps == 2
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-roofline', '--mask-steps', '0'])
+    a = m.parse()
+    assert a.no_roofline and not a.no_cpu_baseline and a.mask_steps == 0
+
+
+def test_bench_dump_outputs_keeps_every_bit(tmp_path, monkeypatch):
+    """--dump-outputs: the output ciphertext's u64 words come back exactly from
+    the two float64 halves, the decryption as given; an output above the size
+    cap is cut to the same seeded sample every time."""
+    m = _bench_module()
+    words = np.random.default_rng(5).integers(0, 1 << 60, size=(2, 3, 16), dtype=np.uint64)
+    words[0, 0, :2] = (0, (1 << 60) - 1)
+
+    class Out:
+        def data(self):
+            return words.copy()
+
+    y = np.linspace(0, 1, 8, dtype=np.float32)
+    d = tmp_path / 'dump'
+    m.dump_outputs(str(d), Out(), y)
+    got = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+    assert sorted(got) == ['ct_words_hi.npy', 'ct_words_lo.npy', 'sorted.npy']
+    assert all(v.dtype == np.float64 for v in got.values())
+    lo, hi = got['ct_words_lo.npy'].astype(np.uint64), got['ct_words_hi.npy'].astype(np.uint64)
+    assert np.array_equal((hi << np.uint64(32)) | lo, words)
+    assert np.array_equal(got['sorted.npy'], y.astype(np.float64))
+    assert m.DUMP_MAX_WORDS * 2 * 8 + 8 * (1 << 17) < 64e6  # two float64 files + the largest decryption
+    monkeypatch.setattr(m, 'DUMP_MAX_WORDS', 10)
+    m.dump_outputs(str(d), Out(), y)
+    cut = np.load(d / 'ct_words_lo.npy')
+    m.dump_outputs(str(tmp_path / 'again'), Out(), y)
+    assert cut.shape == (10,) and np.array_equal(cut, np.load(tmp_path / 'again' / 'ct_words_lo.npy'))
+
+
 @pytest.mark.parametrize('world,ndev,local,want', [
     (1, 8, 1, 'none'),     # one rank: no exchange
     (8, 8, 8, 'rccl'),     # the driver's 8-GPU node: one GPU per rank
