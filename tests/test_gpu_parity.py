@@ -583,6 +583,8 @@ def test_relinearised_products_large_rings(logN, L):
         with F.KernelClock(gpu) as clk:  # (advisor r5: the fused kernel must be the one that ran)
             st = gpu.mul(gpu.stack(gy[:cnt]), gpu.stack(gy[::-1][:cnt]))
         assert any(k.startswith('k_ntt_row_ks') for k in clk.stats), sorted(clk.stats)
+        # 40-bit scaling primes: the HMult tail's ModDown + rescale is the fp64 kernel
+        assert any(k.startswith('k_moddown_rescale_fp<') for k in clk.stats), sorted(clk.stats)
         for m in (0, 7, cnt - 1):
             same(gpu.member(st, m), orc.mul(ys[m], ys[::-1][m]))
     lo = [orc.mul(orc.mul(y, xs[1]), xs[2]) for y in ys[:5]]
