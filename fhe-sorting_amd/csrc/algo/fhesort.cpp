@@ -48,6 +48,17 @@ size_t ps_chunk() {
     }();
     return v;
 }
+// FHE_MUL_FOLD_SCALARS (A/B, default 1): the a + a in front of 2 T_i T_j at equal
+// levels is formed in the product's tensor pass (Engine::mul_add's a_add with the
+// operand itself: add_mod(a, a, q) on load, the words of the separate k_add);
+// 0: the separate launch
+bool fold_scalars() {
+    static const bool v = [] {
+        const char *e = std::getenv("FHE_MUL_FOLD_SCALARS");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return v;
+}
 
 // Levels OpenFHE's EvalChebyshevSeriesPS consumes for a degree-d series: the
 // reference's multDepth tables (src/sort_algo.h:87-201) budget these, and its
@@ -516,7 +527,12 @@ struct PSOpenFHE {
     CtPtr twice_prod(const Ciphertext &a, const Ciphertext &b, const Ciphertext *x, double cx) {
         const Ciphertext *lo = &a, *hi = &b;
         if (lo->level > hi->level) std::swap(lo, hi);
-        CtPtr a2 = lo->level < hi->level ? cc.mul_const_to(*lo, 2.0, hi->level) : cc.add(*lo, *lo);
+        // equal levels: (lo + lo) hi with the sum formed on load in the tensor pass
+        // (a square doubles its left operand only)
+        if (lo->level == hi->level && fold_scalars())
+            return cc.mul_add(*lo, *hi, x ? std::vector<const Ciphertext *>{x} : std::vector<const Ciphertext *>{},
+                              x ? std::vector<double>{cx} : std::vector<double>{}, nullptr, lo);
+        CtPtr a2 =lo->level < hi->level ? cc.mul_const_to(*lo, 2.0, hi->level) : cc.add(*lo, *lo);
         if (!x) return cc.mul(*a2, *hi);
         return cc.mul_add(*a2, *hi, {x}, {cx});
     }

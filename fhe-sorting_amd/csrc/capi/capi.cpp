@@ -284,6 +284,15 @@ int fhe_sub(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, fhe_ct **out) {
 int fhe_mul_relin(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, fhe_ct **out) {
     return guard([&] { *out = wrap(ctx->eng->mul(*a->p, *b->p)); });
 }
+int fhe_mul_add(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *const *xs, const double *c, int m,
+                const fhe_ct *raw, const fhe_ct *a_add, fhe_ct **out) {
+    return guard([&] {
+        std::vector<const Ciphertext *> v;
+        for (int i = 0; i < m; ++i) v.push_back(xs[i]->p.get());
+        *out = wrap(ctx->eng->mul_add(*a->p, *b->p, v, std::vector<double>(c, c + m), raw ? raw->p.get() : nullptr,
+                                      a_add ? a_add->p.get() : nullptr));
+    });
+}
 int fhe_add_const(fhe_ctx *ctx, const fhe_ct *a, double c, fhe_ct **out) {
     return guard([&] { *out = wrap(ctx->eng->add_const(*a->p, c)); });
 }

@@ -131,6 +131,13 @@ struct NttFuse {
     // limb zs0 + z for z < zn0, else zs1 + z - zn0
     int zs0 = 0, zn0 = 1 << 30, zs1 = 0;
     __host__ __device__ int limb_of(int z) const { return z < zn0 ? zs0 + z : zs1 + (z - zn0); }
+    // one-digit HMult tail (ntt_forward_multail_own) instead of x: d2 [members][.][n]
+    // (member stride seg_d2) and the relinearisation key's digit 0, [2][nall][n]
+    // (last, so the other modes' kernel arguments keep their offsets)
+    const u64 *d2 = nullptr;
+    size_t seg_d2 = 0;
+    const u64 *key = nullptr;
+    int nall = 0;
 };
 // inverse NTT reading the input from `src` (segment z, limb l at src + z*seg_src + l*n), writing dst
 void ntt_inverse_from(u64 *dst, const u64 *src, size_t seg_src, int limbs, int segs, size_t seg, const int *pmap,
@@ -139,6 +146,11 @@ void ntt_inverse_from(u64 *dst, const u64 *src, size_t seg_src, int limbs, int s
 void ntt_forward_rescale(u64 *tmp, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st);
 // HMult tail: out = (x + d * c2 - NTT(corr)) * c1 (corr is overwritten by the first pass only)
 void ntt_forward_multail(u64 *corr, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st);
+// HMult tail of a one-digit key switch (ell <= alpha; rings 2^16, 2^17): as
+// ntt_forward_multail with x[z][l] = d2[z / 2][l] * key[z & 1][l] formed in the
+// row pass (F.d2, F.key, F.nall; F.x unused) -- the own-digit key product of
+// every Q limb l < ell - 1, the same residues ntt_row_ks / ks_inner would store
+void ntt_forward_multail_own(u64 *corr, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st);
 // key-switch ModDown finish: out = (x - NTT(conv)) * c1 + d (d on even segments, member z / 2)
 void ntt_forward_ksfinish(u64 *conv, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st);
 // one row pass (forward: the second pass; inverse: the first) alone, for kernel timing
@@ -279,9 +291,11 @@ void ntt_forward_mapped_cols(u64 *data, int count, int segs, size_t seg, const i
 // fp_only: the targets of integer-class primes are left to the caller (their
 // row pass: ntt_forward_mapped_rows; their inner product: ks_inner over the
 // integer runs, ntt_class_runs) -- measured faster there
+// tfirst: only the targets t >= tfirst (one-digit HMult: ell - 1, the limbs
+// below it are left to ntt_forward_multail_own)
 void ntt_row_ks(u64 *acc, const u64 *ext, const u64 *dntt, const u64 *key, int ell, int K, int nall, int alpha,
                 int digits, const int *pmap_ext, int members, KsStrides str, KsFold fold, const NttTables &T,
-                hipStream_t st, bool fp_only = false);
+                hipStream_t st, bool fp_only = false, int tfirst = 0);
 // the row pass alone over mapped limbs (second half of ntt_forward_mapped)
 void ntt_forward_mapped_rows(u64 *data, int count, int segs, size_t seg, const int *smap, const int *pmap,
                              const NttTables &T, hipStream_t st);

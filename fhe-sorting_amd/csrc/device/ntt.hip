@@ -576,9 +576,12 @@ int &row_shfl_enabled() {
 // out = (x + d * c2 - NTT) * c1 (fused ModDown+rescale finish of an HMult);
 // 4 row pass stores out = (x - NTT) * c1 + d (the ModDown finish of a key
 // switch: x the accumulators, c1 = P^-1, d the permuted c0 added to the even
-// segments, member z / 2 at (z / 2) * seg_d, or none).
-// Modes 2-4 do not write `data` back.
-enum { NTT_PLAIN = 0, NTT_LIFT = 1, NTT_RESCALE = 2, NTT_MULTAIL = 3, NTT_KSFINISH = 4 };
+// segments, member z / 2 at (z / 2) * seg_d, or none); 5 mode 3 of a one-digit
+// HMult, whose accumulator x on every Q limb below the last is the own-digit
+// key product d2 * key: the row pass forms it itself from the member's d2 row
+// and the segment's key row (even z: b, odd z: a), so no accumulator is read.
+// Modes 2-5 do not write `data` back.
+enum { NTT_PLAIN = 0, NTT_LIFT = 1, NTT_RESCALE = 2, NTT_MULTAIL = 3, NTT_KSFINISH = 4, NTT_MULTAIL_OWN = 5 };
 
 // COLS: the transform index is a column `col`, element idx sits at idx * 2^k2 + col.
 // ROWS: the transform index is a row `hi`, element idx sits at hi * 2^PB + idx.
@@ -686,27 +689,45 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
     // extra VGPRs do not)
     // (FP rows: FHE_NTT_FP_EPI_PRE=0 loads them in the store loop instead -- A/B)
     constexpr bool EPI_PRE = MODE == NTT_RESCALE ? FHE_NTT_FP_EPI_PRE : FHE_NTT_FP_EPI_PRE_MT;
-    constexpr bool EPI_X = !COLS && (MODE == NTT_RESCALE || MODE == NTT_MULTAIL || MODE == NTT_KSFINISH) &&
-                           (!FP || EPI_PRE);
-    constexpr bool EPI_D = !COLS && (MODE == NTT_MULTAIL || MODE == NTT_KSFINISH) && (!FP || EPI_PRE);
+    constexpr bool OWN = MODE == NTT_MULTAIL_OWN, MT = MODE == NTT_MULTAIL || OWN;
+    constexpr bool EPI_X = !COLS && (MODE == NTT_RESCALE || MT || MODE == NTT_KSFINISH) && (!FP || EPI_PRE);
+    constexpr bool EPI_D = !COLS && (MT || MODE == NTT_KSFINISH) && (!FP || EPI_PRE);
     // key-switch finish: only c0 segments (even z) take the added polynomial
     const bool has_d = MODE == NTT_KSFINISH ? (F.d != nullptr && !(zseg & 1)) : true;
     const size_t d_base = MODE == NTT_KSFINISH ? (size_t)(zseg >> 1) * F.seg_d : (size_t)zseg * F.seg_d;
+    // one-digit HMult: the accumulator of element idx is d2 * key (k_ntt_row_ks'
+    // own-digit product, its indexing): the same residue in [0, 2q) -- FP limbs the
+    // centred fp64 product + q, integer limbs the canonical Barrett product
+    // (the prime's Barrett constants are loaded here for that form alone, so the
+    // other modes' code stays what it was)
+    const Mod mo = OWN && !FP ? Tb.mods[p] : Mod{};
+    const u64 *const own_d = OWN ? F.d2 + (size_t)(zseg >> 1) * F.seg_d2 + (size_t)limb * n + tid_global * LEN : nullptr;
+    const u64 *const own_k = OWN ? F.key + ((size_t)(zseg & 1) * F.nall + p) * n + tid_global * LEN : nullptr;
+    auto own_acc = [&](int idx) -> u64 {
+        const u64 dv = own_d[idx], kv = own_k[idx];
+        if constexpr (FP) {
+            const double pr = fp_mulmod(fp_in(dv, FP_TWO52), fp_in(kv, FP_TWO52), A.q, A.qi);
+            return fp_out(fp_reduce(pr, A.q, A.qi), FP_TWO52 + A.q);
+        } else {
+            return mul_barrett(dv, kv, mo);
+        }
+    };
     u64 ex[EPI_X ? E : 1], ed[EPI_D ? E : 1];
     if (EPI_X) {
         const size_t lo = (size_t)limb * n + tid_global * LEN;
 #pragma unroll
         for (int r = 0; r < E; ++r) {
             const int idx = SH ? row_final_index<true>(t, r) : t + T * r;  // where the pass leaves element r
-            ex[r] = valid ? F.x[(size_t)zseg * F.seg_x + lo + idx] : 0;
+            if constexpr (OWN) ex[r] = valid ? own_acc(idx) : 0;
+            else ex[r] = valid ? F.x[(size_t)zseg * F.seg_x + lo + idx] : 0;
             if (EPI_D) ed[EPI_D ? r : 0] = valid && has_d ? F.d[d_base + lo + idx] : 0;
         }
     }
     // per-limb epilogue constants (fused row-pass modes)
-    const bool EPI = !COLS && (MODE == NTT_RESCALE || MODE == NTT_MULTAIL || MODE == NTT_KSFINISH);
+    const bool EPI = !COLS && (MODE == NTT_RESCALE || MT || MODE == NTT_KSFINISH);
     const Mod mp = Tb.mods[p];
     const u64 c1 = EPI ? F.c1[limb] : 0, c1s = EPI ? F.c1s[limb] : 0;
-    const u64 c2 = MODE == NTT_MULTAIL ? F.c2[limb] : 0, c2s = MODE == NTT_MULTAIL ? F.c2s[limb] : 0;
+    const u64 c2 = MT ? F.c2[limb] : 0, c2s = MT ? F.c2s[limb] : 0;
     // scaled rescale: out = (K x - v) q_last^-1 = x (K q_last^-1) - v q_last^-1
     const u64 kq = (MODE == NTT_RESCALE && F.scalar) ? mul_shoup(smod64(F.scalar, F.scalar_sh, mp), c1, c1s, q) : 0;
     // row-pass store of transform value v (lazy, [0, 12q)) for element r at in-row index idx
@@ -734,8 +755,11 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
                 o = shoup_fold(xin + 3 * q4 - v, c1, c1s, nq);
             }
             F.out[z * F.seg_out + lo + idx] = o >= q ? o - q : o;
-        } else if (MODE == NTT_MULTAIL) {  // (acc + d c2 - v) c1, acc + d c2 + 12q - v < 15q
-            const u64 acc = EPI_X ? ex[EPI_X ? r : 0] : F.x[z * F.seg_x + lo + idx];
+        } else if (MT) {  // (acc + d c2 - v) c1, acc + d c2 + 12q - v < 15q (OWN: acc < 2q, so < 16q < 2^64)
+            u64 acc;
+            if constexpr (EPI_X) acc = ex[EPI_X ? r : 0];
+            else if constexpr (OWN) acc = own_acc(idx);
+            else acc = F.x[z * F.seg_x + lo + idx];
             const u64 dd = EPI_D ? ed[EPI_D ? r : 0] : F.d[z * F.seg_d + lo + idx];
             const u64 tt = acc + shoup_fold(dd, c2, c2s, nq) + 3 * q4 - v;
             const u64 o = shoup_fold(tt, c1, c1s, nq);
@@ -1350,7 +1374,8 @@ int &ntt_full_mask() {
 template <bool COLS, bool FWD, int MODE>
 constexpr int full_bit() {
     return FWD ? (COLS ? (MODE == NTT_LIFT ? 2 : 1)
-                       : MODE == NTT_RESCALE ? 8 : MODE == NTT_MULTAIL ? 16 : MODE == NTT_KSFINISH ? 128 : 4)
+                       : MODE == NTT_RESCALE ? 8 : (MODE == NTT_MULTAIL || MODE == NTT_MULTAIL_OWN) ? 16
+                       : MODE == NTT_KSFINISH ? 128 : 4)
                : (COLS ? 32 : 64);
 }
 
@@ -1363,7 +1388,8 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
     // bits: 1 inverse rows, 2 every forward row, 4 / 8 / 16 the forward HMult-tail /
     // rescale / key-switch-finish rows only
     const int mode = row_shfl_enabled();
-    const int fwd_bit = MODE == NTT_MULTAIL ? 4 : MODE == NTT_RESCALE ? 8 : MODE == NTT_KSFINISH ? 16 : 0;
+    const int fwd_bit = (MODE == NTT_MULTAIL || MODE == NTT_MULTAIL_OWN) ? 4 : MODE == NTT_RESCALE ? 8
+                        : MODE == NTT_KSFINISH ? 16 : 0;
     const bool sh = CAN_SH && (mode & (FWD ? 2 | fwd_bit : 1)) != 0;
     const int count = 1 << (T.logN - PB);  // columns (COLS) or rows (ROWS)
     dim3 grid((unsigned)segs, (unsigned)((count + NB - 1) / NB), (unsigned)limbs);
@@ -1428,8 +1454,12 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
         auto it = names.find(key);
         if (it == names.end()) it = names.emplace(key, key).first;
         // one read + one write of every limb touched (fused epilogues: + the extra operands)
-        const double extra = MODE == NTT_RESCALE ? 1.0 : MODE == NTT_MULTAIL ? 2.0 : MODE == NTT_KSFINISH ? 1.5 : 0.0;
-        clk->record(slot, it->second.c_str(), (2.0 + extra) * 8.0 * (double)limbs * segs * ((size_t)1 << T.logN));
+        // (one-digit HMult tail: tmp + d + out + half a d2 row per segment, the two key rows once)
+        const double extra = MODE == NTT_RESCALE ? 1.0 : MODE == NTT_MULTAIL ? 2.0
+                             : MODE == NTT_KSFINISH || MODE == NTT_MULTAIL_OWN ? 1.5 : 0.0;
+        const double once = MODE == NTT_MULTAIL_OWN ? 2.0 : 0.0;
+        clk->record(slot, it->second.c_str(),
+                    ((2.0 + extra) * segs + once) * 8.0 * (double)limbs * ((size_t)1 << T.logN));
     }
 }
 
@@ -1712,6 +1742,16 @@ void ntt_forward_multail(u64 *corr, int limbs, int segs, const NttFuse &F, const
     dispatch<false, true, NTT_MULTAIL>(k2, corr, limbs, segs, seg, nullptr, nullptr, T, F, st);
 }
 
+void ntt_forward_multail_own(u64 *corr, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st) {
+    if (limbs <= 0 || segs <= 0) return;
+    if (T.logN != 16 && T.logN != 17)
+        throw std::invalid_argument("ntt_forward_multail_own: the row pass is 256 points (rings 2^16, 2^17)");
+    const int k1 = (T.logN + 1) / 2;
+    const size_t seg = (size_t)limbs << T.logN;
+    dispatch<true, true, NTT_PLAIN>(k1, corr, limbs, segs, seg, nullptr, nullptr, T, F, st);
+    launch_pass<8, 4, false, true, NTT_MULTAIL_OWN>(corr, limbs, segs, seg, nullptr, nullptr, T, F, st);
+}
+
 void ntt_forward_ksfinish(u64 *conv, int limbs, int segs, const NttFuse &F, const NttTables &T, hipStream_t st) {
     if (limbs <= 0 || segs <= 0) return;
     const int k1 = (T.logN + 1) / 2, k2 = T.logN - k1;
@@ -1751,7 +1791,7 @@ std::vector<std::pair<int, int>> ntt_class_runs(const int *pmap, int count, bool
 
 void ntt_row_ks(u64 *acc, const u64 *ext, const u64 *dntt, const u64 *key, int ell, int K, int nall, int alpha,
                 int digits, const int *pmap_ext, int members, KsStrides str, KsFold fold, const NttTables &T,
-                hipStream_t st, bool fp_only) {
+                hipStream_t st, bool fp_only, int tfirst) {
     const int W = ell + K;
     if (T.logN != 16 && T.logN != 17) throw std::invalid_argument("ntt_row_ks: the row pass is 256 points (rings 2^16, 2^17)");
     if (digits < 1 || digits > 8) throw std::invalid_argument("ntt_row_ks: 1..8 digits");
@@ -1768,7 +1808,11 @@ void ntt_row_ks(u64 *acc, const u64 *ext, const u64 *dntt, const u64 *key, int e
     const bool full = members % (1 << lmb) == 0;
     const dim3 blk(NTB);
     for (int cls = fp_only ? 1 : 0; cls < 2; ++cls) {
-        const std::vector<std::pair<int, int>> runs = ntt_class_runs(pmap_ext, W, cls == 1, T);
+        std::vector<std::pair<int, int>> runs;
+        for (auto r : ntt_class_runs(pmap_ext, W, cls == 1, T)) {  // the class's targets t >= tfirst
+            const int lo = std::max(r.first, tfirst), hi = r.first + r.second;
+            if (lo < hi) runs.emplace_back(lo, hi - lo);
+        }
         for (size_t r = 0; r < runs.size(); r += 2) {
             NttFuse Fz;
             Fz.zs0 = runs[r].first;

@@ -359,6 +359,17 @@ struct Engine::Impl {
         }();
         return on;
     }
+    // FHE_MULTAIL_OWN (A/B, default 1): a one-digit HMult (ell <= alpha; 124 of the
+    // N=1024 sort's 162 stacked HMults) leaves the own-digit key product of its Q
+    // limbs below ell - 1 to the closing row pass (k_ntt_fwd_row<5, ...>) instead of
+    // storing it from k_ntt_row_ks and reading it back; 0: the accumulator path
+    static bool multail_own() {
+        static const bool on = [] {
+            const char *e = std::getenv("FHE_MULTAIL_OWN");
+            return e ? std::atoi(e) != 0 : true;
+        }();
+        return on;
+    }
     // cols_only: the forward NTT's column pass alone (the row pass runs fused
     // with the key switch, mul_tail)
     std::shared_ptr<DevMem> modup(const u64 *d, size_t ell, int members, size_t d_stride, bool cols_only = false) {
@@ -476,11 +487,18 @@ struct Engine::Impl {
         fold.member = 2 * ell * nn;
         fold.w = LT.pmod[ell - 1];
         fold.ws = LT.pmod_s[ell - 1];
+        // one digit (ell <= alpha): every Q limb is an own-digit limb, its accumulator
+        // the element-wise product d2 * key.  The closing row pass forms that product
+        // itself for the limbs below ell - 1 (ntt_forward_multail_own), so only
+        // q_last (with the fold) and the special primes go through ntt_row_ks and
+        // the Q rows of acc below ell - 1 are never written or read
+        const bool own = fused && digits == 1 && ell >= 2 && ks_fuse_int() && multail_own();
         if (fused) {
             // FP targets: row pass + inner product fused; integer targets (q_0 and
             // the special primes): their row pass ran in modup, ks_inner here
             dev::ntt_row_ks(acc, e, d2, static_cast<u64 *>(ks->relin->p), (int)ell, P.K, (int)P.nall(), P.alpha, digits,
-                            ext(ell), members, str, fold, T, st, /*fp_only*/ !ks_fuse_int());
+                            ext(ell), members, str, fold, T, st, /*fp_only*/ !ks_fuse_int(),
+                            /*tfirst*/ own ? (int)ell - 1 : 0);
             const auto runs = ks_fuse_int() ? std::vector<std::pair<int, int>>{}
                                             : dev::ntt_class_runs(ext(ell), (int)W, false, T);
             for (size_t r = 0; r < runs.size(); r += 2) {
@@ -513,6 +531,15 @@ struct Engine::Impl {
         F.c1s = pqlinv_s + ell * P.nq();
         F.c2 = pmod;
         F.c2s = pmod_s;
+        if (own) {
+            F.x = nullptr;
+            F.d2 = d2;
+            F.seg_d2 = ell * nn;
+            F.key = static_cast<const u64 *>(ks->relin->p);
+            F.nall = (int)P.nall();
+            dev::ntt_forward_multail_own(corr, (int)(ell - 1), segs, F, T, st);
+            return;
+        }
         dev::ntt_forward_multail(corr, (int)(ell - 1), segs, F, T, st);
     }
     // out [segs][ell-1][n] = Rescale(K * in) from the first ell limbs of

@@ -103,6 +103,7 @@ _SIGS = {
     'fhe_add_plain': (C.c_int, [vp, vp, vp, PP]),
     'fhe_mul_relin': (C.c_int, [vp, vp, vp, PP]),
     'fhe_square_relin': (C.c_int, [vp, vp, PP]),
+    'fhe_mul_add': (C.c_int, [vp, vp, vp, PP, dp, C.c_int, vp, vp, PP]),
     'fhe_rotate': (C.c_int, [vp, vp, C.c_int, PP]),
     'fhe_rotate_hoisted': (C.c_int, [vp, vp, ip, C.c_int, PP]),
     'fhe_linear_sum_to': (C.c_int, [vp, PP, dp, C.c_int, C.c_int, PP]),
@@ -607,6 +608,13 @@ class Context:
     def add_plain(self, a, p): return self._new(lib().fhe_add_plain, a.h, p.h)
     def mul(self, a, b): return self._new(lib().fhe_mul_relin, a.h, b.h)
     def square(self, a): return self._new(lib().fhe_square_relin, a.h)
+
+    def mul_add(self, a, b, xs=(), cs=(), raw=None, a_add=None):
+        """(a [+ a_add]) * b + sum_i cs[i] xs[i] [+ raw], one relinearisation and one rescale"""
+        arr = (C.c_void_p * max(1, len(xs)))(*[x.h for x in xs])
+        c = np.ascontiguousarray(cs, dtype=np.float64)
+        return self._new(lib().fhe_mul_add, a.h, b.h, arr, _dbl(c), len(xs), None if raw is None else raw.h,
+                         None if a_add is None else a_add.h)
     def rotate(self, a, k): return self._new(lib().fhe_rotate, a.h, k)
 
     def rotate_hoisted(self, a, ks):

@@ -151,6 +151,12 @@ int fhe_add_plain(fhe_ctx *ctx, const fhe_ct *a, const fhe_pt *p, fhe_ct **out);
 /* EvalMultAndRelinearize / EvalMult(ct,ct) / EvalSquare (src/sign.cpp:23-33; sort_algo.h:730) */
 int fhe_mul_relin(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, fhe_ct **out);
 int fhe_square_relin(fhe_ctx *ctx, const fhe_ct *a, fhe_ct **out);
+/* (a [+ a_add]) * b + sum_i c_i x_i [+ raw] with one relinearisation and one rescale (the
+   Paterson-Stockmeyer products of fhe_cheb_ps): m summands x_i at levels <= a's, formed at the
+   product's pre-rescale scale; raw (or NULL) a ciphertext of a's level added to the tensor as it
+   is; a_add (or NULL) a ciphertext of a's level and batch added to a first */
+int fhe_mul_add(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *const *xs, const double *c, int m,
+                const fhe_ct *raw, const fhe_ct *a_add, fhe_ct **out);
 /* EvalRotate(ct, k) (src/rotation.h:224,231); FHE_ENOKEY if k has no key */
 int fhe_rotate(fhe_ctx *ctx, const fhe_ct *a, int k, fhe_ct **out);
 /* EvalFastRotationPrecompute + EvalFastRotation (src/rotation.h:281,342-346) */
