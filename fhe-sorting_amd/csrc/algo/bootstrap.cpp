@@ -306,20 +306,39 @@ CtPtr Bootstrapper::slotsToCoeffs(const Ciphertext &x) {
     return y;
 }
 
-CtPtr Bootstrapper::evalBootstrap(const Ciphertext &in) {
+CtPtr Bootstrapper::adjust(const Ciphertext &in) {
     const int L = cc.params().L;
-    if (in.batch != 1) throw std::invalid_argument("bootstrap: one ciphertext at a time");
     if (in.slots != cfg.slots) throw std::invalid_argument("bootstrap: ciphertext slots differ from the setup's");
     if (in.level >= L)
         throw std::runtime_error("bootstrap: no level left for the scale adjustment (level " + std::to_string(in.level) +
                                  " == multDepth)");
     const double q0 = (double)cc.params().primes[0];
-    CtPtr x = cc.mul_const_to(in, std::ldexp(q0, -cfg.correctionBits) / cc.delta(L), L);
-    x = cc.mod_raise(*x);
+    return cc.mul_const_to(in, std::ldexp(q0, -cfg.correctionBits) / cc.delta(L), L);
+}
+
+CtPtr Bootstrapper::refresh(const Ciphertext &adjusted) {
+    cc.ctr.boot_calls += 1;
+    cc.ctr.boot_cts += (u64)adjusted.batch;
+    CtPtr x = cc.mod_raise(adjusted);
     for (const auto &ks : traceChunks(cc.params().n, cfg.slots)) x = cc.rotate_sum_hoisted(*x, ks);  // partial trace
     x = coeffsToSlots(*x);
     x = evalMod(*x);
     return slotsToCoeffs(*x);
+}
+
+// a stack is refreshed member-wise in the same launches (every step takes stacks)
+CtPtr Bootstrapper::evalBootstrap(const Ciphertext &in) { return refresh(*adjust(in)); }
+
+CtPtr Bootstrapper::evalBootstrapMany(const std::vector<const Ciphertext *> &cts) {
+    if (cts.empty()) throw std::invalid_argument("bootstrap: no ciphertexts");
+    if (cts.size() == 1) return evalBootstrap(*cts[0]);
+    std::vector<CtPtr> a;
+    std::vector<const Ciphertext *> p;
+    for (const Ciphertext *c : cts) {
+        a.push_back(adjust(*c));
+        p.push_back(a.back().get());
+    }
+    return refresh(*cc.stack(p));
 }
 
 }  // namespace fhe

@@ -44,9 +44,16 @@ class Bootstrapper {
     std::vector<int> rotationIndices() const;
     void keyGen();          // EvalBootstrapKeyGen: rotation keys + conjugation key
     int depth() const;      // output level of evalBootstrap
-    // EvalBootstrap: input level <= L-1 (one level pays the scale adjustment)
+    // EvalBootstrap: input level <= L-1 (one level pays the scale adjustment).
+    // A stack is refreshed member-wise in the same launches (the transforms'
+    // keys and plaintexts are read once per member block), word for word what
+    // each member alone gives.
     CtPtr evalBootstrap(const Ciphertext &ct);
-    // the stages on their own (parity tests)
+    // several ciphertexts or stacks, at any levels <= L-1, refreshed as one
+    // stack in the order given: each is brought to level L on its own (the
+    // scale adjustment), the rest runs once
+    CtPtr evalBootstrapMany(const std::vector<const Ciphertext *> &cts);
+    // the stages on their own (parity tests); stacks as well
     CtPtr coeffsToSlots(const Ciphertext &raised);
     CtPtr evalMod(const Ciphertext &x);
     CtPtr slotsToCoeffs(const Ciphertext &x);
@@ -69,6 +76,8 @@ class Bootstrapper {
 
   private:
     CtPtr transform(const Ciphertext &x, const Level &lv, int tag);
+    CtPtr adjust(const Ciphertext &in);  // checks + the scale adjustment to level L
+    CtPtr refresh(const Ciphertext &x);  // ModRaise .. SlotsToCoeffs of adjust()'s output
     std::map<std::pair<int, int>, std::vector<std::vector<PtPtr>>> pts;  // (tag, level) -> [giant][baby]
 };
 

@@ -774,6 +774,55 @@ CtPtr Comparison::compare(Engine &cc, const Ciphertext &a, const Ciphertext &b, 
     return cc.mul_const(*s, 0.5);
 }
 
+void Comparison::compare2(Engine &cc, const Ciphertext &a, const Ciphertext &b1, const Ciphertext &b2, SignFunc func,
+                          const SignConfig &cfg, CtPtr &c1, CtPtr &c2) {
+    if (func != SignFunc::CompositeSign)
+        throw std::invalid_argument("sign: only SignFunc::CompositeSign is implemented on the GPU path");
+    const int n = cfg.compos.n;
+    if (n != 3 && n != 4) throw std::invalid_argument("compositeSign: n must be 3 or 4");
+    const int L = cc.params().L;
+    // the pair: ys (one 2-member stack) once both chains sit at one level, y1 / y2 until then
+    CtPtr y1, y2, ys;
+    if (b1.level == b2.level) {
+        ys = cc.sub_stacked(a, {&b1, &b2});
+    } else {
+        y1 = cc.sub(a, b1);
+        y2 = cc.sub(a, b2);
+    }
+    auto need = [&](const Ciphertext &c) { return cfg.boot && L - c.level < n + 2; };  // compositeSignN's lazy
+    auto step = [&](bool isg) {
+        auto fn = [&](const Ciphertext &v) { return isg ? (n == 3 ? g3(cc, v) : g4(cc, v)) : (n == 3 ? f3(cc, v) : f4(cc, v)); };
+        if (ys) {
+            if (need(*ys)) ys = cfg.boot(*ys);
+            ys = fn(*ys);
+            return;
+        }
+        const bool n1 = need(*y1), n2 = need(*y2);
+        if (n1 && n2 && cfg.bootMany) {
+            ys = fn(*cfg.bootMany({y1.get(), y2.get()}));
+            return;
+        }
+        if (n1) y1 = cfg.boot(*y1);
+        if (n2) y2 = cfg.boot(*y2);
+        y1 = fn(*y1);
+        y2 = fn(*y2);
+    };
+    step(true);
+    for (int i = 1; i < cfg.compos.dg; ++i) step(true);
+    for (int i = 0; i < cfg.compos.df; ++i) step(false);
+    if (ys) {
+        cc.add_const_inplace(ys, 1.0);
+        ys = cc.mul_const(*ys, 0.5);
+        c1 = cc.member(*ys, 0);
+        c2 = cc.member(*ys, 1);
+        return;
+    }
+    cc.add_const_inplace(y1, 1.0);
+    cc.add_const_inplace(y2, 1.0);
+    c1 = cc.mul_const(*y1, 0.5);
+    c2 = cc.mul_const(*y2, 0.5);
+}
+
 CtPtr Comparison::indicator(Engine &cc, const Ciphertext &x, double c, SignFunc f, const SignConfig &cfg) {
     CtPtr d1 = cc.add_const(x, c);
     CtPtr d2 = cc.add_const(x, -c);

@@ -36,6 +36,9 @@ struct SignConfig {
     // run on a bootstrapped input whenever fewer than depth + 2 levels remain
     // (the context's depth is the reference's Cfg.multDepth)
     std::function<CtPtr(const Ciphertext &)> boot;
+    // optional: several ciphertexts (any levels) bootstrapped in one pass, the
+    // result a stack in the order given (Bootstrapper::evalBootstrapMany)
+    std::function<CtPtr(const std::vector<const Ciphertext *> &)> bootMany;
     SignConfig() = default;
     explicit SignConfig(CompositeSignConfig c) : compos(c) {}
     SignConfig(CompositeSignConfig c, int depth) : compos(c), multDepth(depth) {}
@@ -65,6 +68,13 @@ CtPtr sign(const Ciphertext &x, Engine &cc, SignFunc func, const SignConfig &cfg
 class Comparison {
   public:
     CtPtr compare(Engine &cc, const Ciphertext &a, const Ciphertext &b, SignFunc f, const SignConfig &cfg);
+    // c1 = compare(a, b1), c2 = compare(a, b2), word for word, with the two sign
+    // chains run as one 2-member stack from the first point at which they sit at
+    // one level (at once when b1 and b2 do; otherwise after the first lazy
+    // bootstrap both need, taken in one pass through cfg.bootMany); c1, c2 are
+    // then member views of that stack
+    void compare2(Engine &cc, const Ciphertext &a, const Ciphertext &b1, const Ciphertext &b2, SignFunc f,
+                  const SignConfig &cfg, CtPtr &c1, CtPtr &c2);
     CtPtr indicator(Engine &cc, const Ciphertext &x, double c, SignFunc f, const SignConfig &cfg);
 };
 

@@ -204,7 +204,14 @@ void concurrently(A &&main, B &&lane) {
 
 void Sorter::checkLevel2(CtPtr &c1, CtPtr &c2, int need, const SignConfig &cfg) {
     const int L = cc.params().L;
-    if (!laneEng || L - c1->level >= need + 1 || L - c2->level >= need + 1) {
+    if (stackPairs && cfg.bootMany && L - c1->level < need + 1 && L - c2->level < need + 1) {
+        const CtPtr b = cfg.bootMany({c1.get(), c2.get()});  // both need it: one pass over the pair
+        c1 = cc.member(*b, 0);
+        c2 = cc.member(*b, 1);
+        bootstraps += 2;
+        return;
+    }
+    if (stackPairs || !laneEng || L - c1->level >= need + 1 || L - c2->level >= need + 1) {
         checkLevel(c1, need, cfg);  // at most one bootstrap: on this engine
         checkLevel(c2, need, cfg);
         return;
@@ -544,6 +551,10 @@ void Sorter::comparisonForSort2(const CtPtr &x, const std::vector<std::vector<in
     CtPtr r1, r2;
     rightRotateForSort(x, ind, logDist, slope, r1, &fix);
     rightRotateForSort(r1, ind, logDist, slope, r2, nullptr);
+    if (stackPairs) {
+        comp.compare2(cc, *x, *r1, *r2, SignFunc::CompositeSign, cfg, c1, c2);
+        return;
+    }
     if (!laneEng) {
         c1 = comp.compare(cc, *x, *r1, SignFunc::CompositeSign, cfg);
         c2 = comp.compare(cc, *x, *r2, SignFunc::CompositeSign, cfg);

@@ -52,6 +52,11 @@ class Sorter {
     // threads at once; every operation is the same, so the words are too.
     Engine *laneEng = nullptr;
     SignConfig laneCfg;
+    // the two comparisons of a k = 5 stage as one 2-member stack on this engine
+    // (Comparison::compare2), their bootstraps included, and a pair that
+    // checkLevel2 has to bootstrap refreshed in one pass (cfg.bootMany); no lane
+    // thread is used for the pair.  Same words as with it off.
+    bool stackPairs = false;
     // SortUtils::fcnL (kk = 1: returns {fcnL(x0, x1, c0)}) or the kk-sorter,
     // kk = 2..5 (SortUtils.cpp:5-208), on their own: SortUtilsTest's cases
     std::vector<CtPtr> kSorter(int kk, const std::vector<CtPtr> &x, const std::vector<CtPtr> &cmp);

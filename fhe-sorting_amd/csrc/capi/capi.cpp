@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -30,6 +31,7 @@ struct fhe_ctx {
     int sort_lanes = 2;
     bool mask_cache = true;  // fhe_set_mask_cache
     std::unique_ptr<Engine> kway_lane;  // the k-way sorter's second lane (forked on first use)
+    bool kway_stack = false;            // fhe_set_kway_stack (initial value: FHE_KWAY_STACK)
 };
 struct fhe_ct {
     CtPtr p;
@@ -108,6 +110,7 @@ int fhe_ctx_create(const fhe_params *p, int device, fhe_ctx **out) {
         c->eng = std::make_unique<Engine>(p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum, device,
                                           p->seed);
         c->params = wire::CtxParams{p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum, p->seed};
+        if (const char *e = std::getenv("FHE_KWAY_STACK")) c->kway_stack = std::atoi(e) != 0;
         *out = c.release();
     });
 }
@@ -638,8 +641,10 @@ int fhe_kway_sort_boot(fhe_ctx *ctx, const fhe_ct *x, int k, int M, int dg, int 
         if (boot) {
             Bootstrapper *B = boot->b.get();
             cfg.boot = [B](const Ciphertext &c) { return B->evalBootstrap(c); };
+            cfg.bootMany = [B](const std::vector<const Ciphertext *> &c) { return B->evalBootstrapMany(c); };
         }
-        if (ctx->sort_lanes >= 2) {  // the two comparisons of a stage on two streams
+        s.stackPairs = ctx->kway_stack;  // the pair as one stack on this engine: no lane
+        if (ctx->sort_lanes >= 2 && !s.stackPairs) {  // the two comparisons of a stage on two streams
             if (!ctx->kway_lane) ctx->kway_lane = ctx->eng->fork();
             s.laneEng = ctx->kway_lane.get();
             s.laneCfg = cfg;
@@ -989,6 +994,21 @@ int fhe_counters(fhe_ctx *ctx, uint64_t out[7]) {
         out[4] = c.ptmult;
         out[5] = c.constmult;
         out[6] = c.opbytes;
+    });
+}
+int fhe_boot_counters(fhe_ctx *ctx, uint64_t out[2]) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(out);
+        // lane engines merge their counters into the context's engine after every use
+        out[0] = ctx->eng->ctr.boot_calls;
+        out[1] = ctx->eng->ctr.boot_cts;
+    });
+}
+int fhe_set_kway_stack(fhe_ctx *ctx, int on) {
+    return guard([&] {
+        NEED(ctx);
+        ctx->kway_stack = on != 0;
     });
 }
 int fhe_collective_stats(fhe_ctx *ctx, uint64_t out[2]) {

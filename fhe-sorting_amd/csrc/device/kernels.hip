@@ -1648,6 +1648,182 @@ __global__ __launch_bounds__(NT) void k_permute_sum(u64 *out, const u64 *in, KsK
     for (int mb = 0; mb < count; ++mb) r = add_mod(r, in[(size_t)mb * S.a + ln + KK.perm[mb][k]], q);
     out[ln + k] = r;
 }
+// ---------------------------------------- member-blocked (stacked) forms ----
+// The bootstrap's linear transforms and partial trace on a ciphertext stack: a
+// thread owns one (coefficient, target) and MC members.  Whatever does not
+// depend on the member -- the plaintext word, the permutation index and the 2D
+// key words of a baby or a rotation -- is loaded once into registers and serves
+// the MC members; per member only the D gathered ModUp words (and c0) are read.
+// Per member the operation order is that of the single-ciphertext kernel above,
+// so the words are the same.  grid: x = coefficient block, y = target (limb),
+// z = member group; the tail group is guarded.
+template <int D, int MC>
+__global__ __launch_bounds__(NT) void k_lt_inner_mb(u64 *out, const u64 *ext, const u64 *c, LtArgs A, int accumulate,
+                                                    int ell, int W, int nall, int alpha, int members, MbStrides S,
+                                                    const int *pmap_ext, const u64 *pmodq, const u64 *pmodq_s,
+                                                    const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const size_t k = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (k >= n) return;
+    const int t = blockIdx.y;
+    const int m0 = blockIdx.z * MC;
+    const int pt = pmap_ext[t];
+    const Mod m = mods[pt];
+    const bool ql = t < ell;
+    const u64 Pt = ql ? pmodq[t] : 0, Pts = ql ? pmodq_s[t] : 0;
+    const size_t o0 = (size_t)t * n + k, o1 = ((size_t)W + t) * n + k;
+    u64 a0[MC], a1[MC];
+#pragma unroll
+    for (int u = 0; u < MC; ++u) {
+        a0[u] = a1[u] = 0;
+        if (accumulate && m0 + u < members) {
+            const u64 *o = out + (size_t)(m0 + u) * S.out;
+            a0[u] = o[o0];
+            a1[u] = o[o1];
+        }
+    }
+    for (int b = 0; b < A.nb; ++b) {
+        const u64 w = A.pt[b][(size_t)t * n + k];
+        if (!A.key[b]) {
+#pragma unroll
+            for (int u = 0; u < MC; ++u) {
+                if (m0 + u >= members) continue;
+                u64 b0 = 0, b1 = 0;
+                if (ql) {
+                    const u64 *cm = c + (size_t)(m0 + u) * S.c;
+                    b0 = mul_shoup(cm[(size_t)t * n + k], Pt, Pts, m.q);
+                    b1 = mul_shoup(cm[((size_t)ell + t) * n + k], Pt, Pts, m.q);
+                }
+                a0[u] = add_mod(a0[u], mul_barrett(b0, w, m), m.q);
+                a1[u] = add_mod(a1[u], mul_barrett(b1, w, m), m.q);
+            }
+            continue;
+        }
+        const u64 *key = A.key[b];
+        const size_t kk = A.perm[b][k];
+        u64 kb[D], ka[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            kb[j] = key[(((size_t)j * 2 + 0) * nall + pt) * n + k];
+            ka[j] = key[(((size_t)j * 2 + 1) * nall + pt) * n + k];
+        }
+#pragma unroll
+        for (int u = 0; u < MC; ++u) {
+            if (m0 + u >= members) continue;
+            const u64 *cm = c + (size_t)(m0 + u) * S.c, *em = ext + (size_t)(m0 + u) * S.ext;
+            u64 x[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const int lo = j * alpha, hi = min((j + 1) * alpha, ell);
+                x[j] = (t >= lo && t < hi) ? cm[((size_t)ell + t) * n + kk] : em[((size_t)j * W + t) * n + kk];
+            }
+            u64 b0 = 0, b1 = 0;
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                b0 = add_mod(b0, mul_barrett(x[j], kb[j], m), m.q);
+                b1 = add_mod(b1, mul_barrett(x[j], ka[j], m), m.q);
+            }
+            if (ql) b0 = add_mod(b0, mul_shoup(cm[(size_t)t * n + kk], Pt, Pts, m.q), m.q);
+            a0[u] = add_mod(a0[u], mul_barrett(b0, w, m), m.q);
+            a1[u] = add_mod(a1[u], mul_barrett(b1, w, m), m.q);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < MC; ++u) {
+        if (m0 + u >= members) continue;
+        u64 *o = out + (size_t)(m0 + u) * S.out;
+        o[o0] = a0[u];
+        o[o1] = a1[u];
+    }
+}
+// k_ks_inner_mk_sum per member of a stack: member m's accumulator pair at
+// m * S.out (+)= sum_i <ext_{i,m} o perm_i, key_i>, input (i, m) at
+// i * st.ext + m * S.ext (own digit: i * st.d + m * S.c)
+template <int D, int MC>
+__global__ __launch_bounds__(NT) void k_ks_inner_mk_sum_mb(u64 *acc, const u64 *ext, const u64 *dntt, KsKeys KK,
+                                                           int count, int accumulate, int ell, int W, int nall,
+                                                           int alpha, int members, MbStrides S, const int *pmap_ext,
+                                                           const Mod *mods, int logN, KsStrides st) {
+    const size_t n = (size_t)1 << logN;
+    const size_t k = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (k >= n) return;
+    const int t = blockIdx.y;
+    const int m0 = blockIdx.z * MC;
+    const int pt = pmap_ext[t];
+    const Mod m = mods[pt];
+    const size_t o0 = (size_t)t * n + k, o1 = ((size_t)W + t) * n + k;
+    u64 a0[MC], a1[MC];
+#pragma unroll
+    for (int u = 0; u < MC; ++u) {
+        a0[u] = a1[u] = 0;
+        if (accumulate && m0 + u < members) {
+            const u64 *o = acc + (size_t)(m0 + u) * S.out;
+            a0[u] = o[o0];
+            a1[u] = o[o1];
+        }
+    }
+    for (int i = 0; i < count; ++i) {
+        const u64 *key = KK.key[i];
+        const uint32_t *perm = KK.perm[i];
+        const size_t kk = perm ? perm[k] : k;
+        u64 kb[D], ka[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            kb[j] = key[(((size_t)j * 2 + 0) * nall + pt) * n + k];
+            ka[j] = key[(((size_t)j * 2 + 1) * nall + pt) * n + k];
+        }
+#pragma unroll
+        for (int u = 0; u < MC; ++u) {
+            if (m0 + u >= members) continue;
+            const u64 *dm = dntt + (size_t)i * st.d + (size_t)(m0 + u) * S.c;
+            const u64 *em = ext + (size_t)i * st.ext + (size_t)(m0 + u) * S.ext;
+            u64 x[D];
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                const int lo = j * alpha, hi = min((j + 1) * alpha, ell);
+                x[j] = (t >= lo && t < hi) ? dm[(size_t)t * n + kk] : em[((size_t)j * W + t) * n + kk];
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                a0[u] = add_mod(a0[u], mul_barrett(x[j], kb[j], m), m.q);
+                a1[u] = add_mod(a1[u], mul_barrett(x[j], ka[j], m), m.q);
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < MC; ++u) {
+        if (m0 + u >= members) continue;
+        u64 *o = acc + (size_t)(m0 + u) * S.out;
+        o[o0] = a0[u];
+        o[o1] = a1[u];
+    }
+}
+// k_permute_sum per member: out[m] (at m * so) (+)= sum_i in_{i,m} o perm_i,
+// input (i, m) at i * S.a + m * sm; a permutation index is read once for the MC
+// members of a thread.  grid: x = n / NT, y = limb, z = member group
+template <int MC>
+__global__ __launch_bounds__(NT) void k_permute_sum_mb(u64 *out, const u64 *in, KsKeys KK, int count, int accumulate,
+                                                       int members, size_t so, size_t sm, Seg S, const Mod *mods,
+                                                       int logN) {
+    const size_t n = (size_t)1 << logN;
+    const size_t ln = (size_t)blockIdx.y * n;
+    const size_t k = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (k >= n) return;
+    const int m0 = blockIdx.z * MC;
+    const u64 q = mods[blockIdx.y].q;
+    u64 r[MC];
+#pragma unroll
+    for (int u = 0; u < MC; ++u) r[u] = (accumulate && m0 + u < members) ? out[(size_t)(m0 + u) * so + ln + k] : 0;
+    for (int i = 0; i < count; ++i) {
+        const size_t kk = KK.perm[i][k];
+#pragma unroll
+        for (int u = 0; u < MC; ++u)
+            if (m0 + u < members) r[u] = add_mod(r[u], in[(size_t)i * S.a + (size_t)(m0 + u) * sm + ln + kk], q);
+    }
+#pragma unroll
+    for (int u = 0; u < MC; ++u)
+        if (m0 + u < members) out[(size_t)(m0 + u) * so + ln + k] = r[u];
+}
 // grid: x = n / NT, y = limb, z = member
 __global__ __launch_bounds__(NT) void k_permute_mk(u64 *out, const u64 *in, KsKeys KK, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -2737,6 +2913,77 @@ void ew_permute_sum(u64 *out, const u64 *in, const KsKeys &keys, int limbs, int 
     if (count > KS_MAXKEYS) throw std::invalid_argument("ew_permute_sum: too many keys");
     hipLaunchKernelGGL(k_permute_sum, pt_grid(logN, limbs, 1), dim3(NT), 0, st, out, in, keys, count, (int)accumulate,
                        Seg{0, in_stride, 0}, mods, logN);
+}
+// member block of a stacked launch: 2 for a pair, else LT_MB_MAX (the tail group guarded)
+template <class F>
+static void dispatch_member_block(int members, F &&f) {
+    if (members <= 2)
+        f(std::integral_constant<int, 2>{});
+    else
+        f(std::integral_constant<int, LT_MB_MAX>{});
+}
+void lt_inner_members(u64 *out, const u64 *ext, const u64 *c, const LtArgs &A, bool accumulate, int ell, int K,
+                      int nall, int alpha, int digits, int members, MbStrides S, const int *pmap_ext, const u64 *pmodq,
+                      const u64 *pmodq_s, const Mod *mods, int logN, hipStream_t st) {
+    if (A.nb <= 0 || members <= 0) return;
+    if (A.nb > LT_MAXB) throw std::invalid_argument("lt_inner: too many babies per launch");
+    const int W = ell + K;
+    int keyed = 0;
+    for (int b = 0; b < A.nb; ++b) keyed += A.key[b] != nullptr;
+    dispatch_member_block(members, [&](auto mcc) {
+        constexpr int MC = decltype(mcc)::value;
+        const int groups = (members + MC - 1) / MC;
+        // per member group: the keys of the keyed babies and every plaintext; per
+        // member: the gathered ext digits, the ciphertext, the accumulator pair
+        // out (and in).  One group (members <= MC):
+        // 8 n [keyed 2 D W + nb W + B (keyed D W + 2 ell + 2 W (1 + accumulate))]
+        const double B = 8.0 *
+                         ((double)groups * ((double)keyed * 2.0 * digits * W + (double)A.nb * W) +
+                          (double)members * ((double)keyed * digits * W + 2.0 * ell + 2.0 * W * (1 + accumulate))) *
+                         ((size_t)1 << logN);
+        const dim3 grid((unsigned)((((size_t)1 << logN) + NT - 1) / NT), (unsigned)W, (unsigned)groups);
+        dispatch_int<1, 8>(digits, [&](auto dc) {
+            constexpr int D = decltype(dc)::value;
+            launch_clocked(inst_name<D, MC>("k_lt_inner_mb"), B, k_lt_inner_mb<D, MC>, grid, dim3(NT), st, out, ext, c, A,
+                           (int)accumulate, ell, W, nall, alpha, members, S, pmap_ext, pmodq, pmodq_s, mods, logN);
+        });
+    });
+}
+void ks_inner_multikey_sum_members(u64 *acc, const u64 *ext, const u64 *dntt, const KsKeys &keys, int count,
+                                   bool accumulate, int ell, int K, int nall, int alpha, int digits, int members,
+                                   MbStrides S, const int *pmap_ext, const Mod *mods, int logN, hipStream_t st,
+                                   KsStrides str) {
+    if (count <= 0 || members <= 0) return;
+    if (count > KS_MAXKEYS) throw std::invalid_argument("ks_inner_multikey_sum: too many keys");
+    const int W = ell + K;
+    dispatch_member_block(members, [&](auto mcc) {
+        constexpr int MC = decltype(mcc)::value;
+        const int groups = (members + MC - 1) / MC;
+        // every key once per member group; per member its ext words and accumulator pair
+        const double B = 8.0 *
+                         ((double)groups * count * 2.0 * digits * W +
+                          (double)members * ((double)count * digits * W + 2.0 * W * (1 + accumulate))) *
+                         ((size_t)1 << logN);
+        const dim3 grid((unsigned)((((size_t)1 << logN) + NT - 1) / NT), (unsigned)W, (unsigned)groups);
+        dispatch_int<1, 8>(digits, [&](auto dc) {
+            constexpr int D = decltype(dc)::value;
+            launch_clocked(inst_name<D, MC>("k_ks_inner_mk_sum_mb"), B, k_ks_inner_mk_sum_mb<D, MC>, grid, dim3(NT), st,
+                           acc, ext, dntt, keys, count, (int)accumulate, ell, W, nall, alpha, members, S, pmap_ext, mods,
+                           logN, str);
+        });
+    });
+}
+void ew_permute_sum_members(u64 *out, const u64 *in, const KsKeys &keys, int limbs, int count, bool accumulate,
+                            size_t in_stride, int members, size_t out_stride, size_t member_stride, const Mod *mods,
+                            int logN, hipStream_t st) {
+    if (limbs <= 0 || count <= 0 || members <= 0) return;
+    if (count > KS_MAXKEYS) throw std::invalid_argument("ew_permute_sum: too many keys");
+    dispatch_member_block(members, [&](auto mcc) {
+        constexpr int MC = decltype(mcc)::value;
+        hipLaunchKernelGGL(k_permute_sum_mb<MC>, pt_grid(logN, limbs, (members + MC - 1) / MC), dim3(NT), 0, st, out, in,
+                           keys, count, (int)accumulate, members, out_stride, member_stride, Seg{0, in_stride, 0}, mods,
+                           logN);
+    });
 }
 void ew_permute_multi(u64 *out, const u64 *in, const KsKeys &keys, int limbs, int count, Seg S, int logN,
                       hipStream_t st) {

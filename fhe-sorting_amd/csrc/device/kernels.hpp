@@ -332,6 +332,28 @@ void lt_inner(u64 *out, const u64 *ext, const u64 *c, const LtArgs &A, bool accu
 // out [limbs][n] (+)= sum_m in_m o keys.perm[m] (member m at m * in_stride)
 void ew_permute_sum(u64 *out, const u64 *in, const KsKeys &keys, int limbs, int count, bool accumulate, size_t in_stride,
                     const Mod *mods, int logN, hipStream_t st);
+// The three above on a stack of `members` ciphertexts (members >= 2; the
+// member-blocked kernels k_lt_inner_mb / k_ks_inner_mk_sum_mb / k_permute_sum_mb):
+// keys, permutations and plaintexts are shared by the members and read once per
+// block of up to LT_MB_MAX members.  Member m's accumulator pair at m * S.out,
+// its ModUp at m * S.ext, its ciphertext (lt) or own-digit polynomial (ks) at
+// m * S.c.  Same words, member by member, as the single forms.
+constexpr int LT_MB_MAX = 4;
+struct MbStrides {
+    size_t out = 0, ext = 0, c = 0;
+};
+void lt_inner_members(u64 *out, const u64 *ext, const u64 *c, const LtArgs &A, bool accumulate, int ell, int K,
+                      int nall, int alpha, int digits, int members, MbStrides S, const int *pmap_ext, const u64 *pmodq,
+                      const u64 *pmodq_s, const Mod *mods, int logN, hipStream_t st);
+// key i < count reads member m's ext at i * str.ext + m * S.ext and own digit at i * str.d + m * S.c
+void ks_inner_multikey_sum_members(u64 *acc, const u64 *ext, const u64 *dntt, const KsKeys &keys, int count,
+                                   bool accumulate, int ell, int K, int nall, int alpha, int digits, int members,
+                                   MbStrides S, const int *pmap_ext, const Mod *mods, int logN, hipStream_t st,
+                                   KsStrides str);
+// out[m] (at m * out_stride) (+)= sum_i in_{i,m} o keys.perm[i], input (i, m) at i * in_stride + m * member_stride
+void ew_permute_sum_members(u64 *out, const u64 *in, const KsKeys &keys, int limbs, int count, bool accumulate,
+                            size_t in_stride, int members, size_t out_stride, size_t member_stride, const Mod *mods,
+                            int logN, hipStream_t st);
 void ks_inner_multikey(u64 *acc, const u64 *ext, const u64 *dntt, const KsKeys &keys, int count, int ell, int K,
                        int nall, int alpha, int digits, const int *pmap_ext, const Mod *mods, int logN,
                        hipStream_t st, KsStrides str);

@@ -1643,10 +1643,9 @@ CtPtr Engine::rotate_members(const Ciphertext &a, const std::vector<long> &ks) {
 
 CtPtr Engine::rotate_sum_hoisted(const Ciphertext &x, const std::vector<long> &ks) {
     auto &I = *impl;
-    if (x.batch != 1) throw std::invalid_argument("rotate_sum_hoisted: one ciphertext at a time");
     if (ks.empty()) return clone(x);
     const size_t nn = n(), ell = x.limbs, ln = ell * nn, W = ell + (size_t)I.P.K;
-    const int digits = I.P.digits_at(ell);
+    const int digits = I.P.digits_at(ell), B = x.batch;
     std::vector<u64> gs;
     for (long k : ks) {
         const u64 g = host::galois_for_rotation(I.P.logN, k);
@@ -1654,10 +1653,15 @@ CtPtr Engine::rotate_sum_hoisted(const Ciphertext &x, const std::vector<long> &k
         if (!I.ks->rotkeys.count(g)) throw NoKeyError("rotate: no rotation key for index " + std::to_string(k));
         gs.push_back(g);
     }
-    auto extm = I.modup(x.data + ln, ell, 1, 2 * ln);
-    auto accm = I.alloc(2 * W * nn * 8), c0m = I.alloc(ln * 8);
+    // a stack: member m's ModUp at m * es, its accumulator pair at m * 2 W n, its c0 sum at m * ln
+    auto extm = I.modup(x.data + ln, ell, B, 2 * ln);
+    auto accm = I.alloc((size_t)B * 2 * W * nn * 8), c0m = I.alloc((size_t)B * ln * 8);
     u64 *acc = static_cast<u64 *>(accm->p), *c0 = static_cast<u64 *>(c0m->p);
     dev::KsStrides str;  // every rotation reads the one hoisted ModUp and x's c1
+    dev::MbStrides mb;
+    mb.out = 2 * W * nn;
+    mb.ext = (size_t)digits * W * nn;
+    mb.c = 2 * ln;
     for (size_t b0 = 0; b0 < gs.size(); b0 += dev::KS_MAXKEYS) {
         const int cnt = (int)std::min<size_t>(dev::KS_MAXKEYS, gs.size() - b0);
         dev::KsKeys KK{};
@@ -1665,26 +1669,32 @@ CtPtr Engine::rotate_sum_hoisted(const Ciphertext &x, const std::vector<long> &k
             KK.key[i] = static_cast<const u64 *>(I.ks->rotkeys.at(gs[b0 + i])->p);
             KK.perm[i] = I.perm(gs[b0 + i]);
         }
-        dev::ew_permute_sum(c0, x.data, KK, (int)ell, cnt, b0 > 0, 0, MODS, LOGN, ST);
-        dev::ks_inner_multikey_sum(acc, static_cast<u64 *>(extm->p), x.data + ln, KK, cnt, b0 > 0, (int)ell, I.P.K,
-                                   (int)I.P.nall(), I.P.alpha, digits, I.ext(ell), MODS, LOGN, ST, str);
+        if (B == 1) {
+            dev::ew_permute_sum(c0, x.data, KK, (int)ell, cnt, b0 > 0, 0, MODS, LOGN, ST);
+            dev::ks_inner_multikey_sum(acc, static_cast<u64 *>(extm->p), x.data + ln, KK, cnt, b0 > 0, (int)ell, I.P.K,
+                                       (int)I.P.nall(), I.P.alpha, digits, I.ext(ell), MODS, LOGN, ST, str);
+        } else {
+            dev::ew_permute_sum_members(c0, x.data, KK, (int)ell, cnt, b0 > 0, 0, B, ln, 2 * ln, MODS, LOGN, ST);
+            dev::ks_inner_multikey_sum_members(acc, static_cast<u64 *>(extm->p), x.data + ln, KK, cnt, b0 > 0, (int)ell,
+                                               I.P.K, (int)I.P.nall(), I.P.alpha, digits, B, mb, I.ext(ell), MODS, LOGN,
+                                               ST, str);
+        }
     }
-    auto t = new_ct(x.level, x.slots, x.scale, ell, 1);
-    I.ks_moddown(acc, ell, 2, t->data, c0, 0);
-    dev::ew_add(t->data, t->data, x.data, (int)ell, 2, seg3(ln, ln, ln), MODS, LOGN, ST);
-    ctr.keyswitch += gs.size();
-    ctr.rotations += gs.size();
-    count_bytes((4.0 * ell + ks_units(ell)) * (double)gs.size() + 6.0 * ell, 1);
+    auto t = new_ct(x.level, x.slots, x.scale, ell, B);
+    I.ks_moddown(acc, ell, 2 * B, t->data, c0, ln);
+    dev::ew_add(t->data, t->data, x.data, (int)ell, 2 * B, seg3(ln, ln, ln), MODS, LOGN, ST);
+    ctr.keyswitch += gs.size() * B;
+    ctr.rotations += gs.size() * B;
+    count_bytes((4.0 * ell + ks_units(ell)) * (double)gs.size() + 6.0 * ell, B);
     return t;
 }
 
 CtPtr Engine::linear_transform_ext(const Ciphertext &x, const std::vector<long> &baby,
                                    const std::vector<LtGiant> &giants) {
     auto &I = *impl;
-    if (x.batch != 1) throw std::invalid_argument("linear_transform_ext: one ciphertext at a time");
     if (x.level >= I.P.L) throw std::runtime_error("linear_transform_ext: no levels left");
     const size_t nn = n(), ell = x.limbs, ln = ell * nn, W = ell + (size_t)I.P.K;
-    const int digits = I.P.digits_at(ell);
+    const int digits = I.P.digits_at(ell), B = x.batch;
     std::vector<const u64 *> bkey(baby.size(), nullptr);
     std::vector<const uint32_t *> bperm(baby.size(), nullptr);
     size_t keyed = 0;
@@ -1697,7 +1707,13 @@ CtPtr Engine::linear_transform_ext(const Ciphertext &x, const std::vector<long> 
         bperm[b] = I.perm(g);
         ++keyed;
     }
-    auto extm = I.modup(x.data + ln, ell, 1, 2 * ln);
+    // a stack: every per-ciphertext buffer below holds B of them, member-major
+    const size_t es = (size_t)digits * W * nn, as = 2 * W * nn;
+    dev::MbStrides mb;
+    mb.out = as;
+    mb.ext = es;
+    mb.c = 2 * ln;
+    auto extm = I.modup(x.data + ln, ell, B, 2 * ln);
     const u64 *ext = static_cast<const u64 *>(extm->p);
     size_t npt = 0;
     auto inner_of = [&](const LtGiant &G, u64 *out) {
@@ -1716,12 +1732,16 @@ CtPtr Engine::linear_transform_ext(const Ciphertext &x, const std::vector<long> 
                 A.perm[i] = bperm[(size_t)bi];
                 A.pt[i] = p->data;
             }
-            dev::lt_inner(out, ext, x.data, A, b0 > 0, (int)ell, I.P.K, (int)I.P.nall(), I.P.alpha, digits, I.ext(ell),
-                          I.pmod, I.pmod_s, MODS, LOGN, ST);
+            if (B == 1)
+                dev::lt_inner(out, ext, x.data, A, b0 > 0, (int)ell, I.P.K, (int)I.P.nall(), I.P.alpha, digits,
+                              I.ext(ell), I.pmod, I.pmod_s, MODS, LOGN, ST);
+            else
+                dev::lt_inner_members(out, ext, x.data, A, b0 > 0, (int)ell, I.P.K, (int)I.P.nall(), I.P.alpha, digits, B,
+                                      mb, I.ext(ell), I.pmod, I.pmod_s, MODS, LOGN, ST);
         }
         npt += G.baby.size();
     };
-    auto accm = I.alloc(2 * W * nn * 8);
+    auto accm = I.alloc((size_t)B * as * 8);
     u64 *acc = static_cast<u64 *>(accm->p);
     bool have_acc = false;
     std::vector<const LtGiant *> shifted;
@@ -1738,25 +1758,25 @@ CtPtr Engine::linear_transform_ext(const Ciphertext &x, const std::vector<long> 
     const int S = (int)shifted.size();
     if (S > 0) {
         // each rotated giant's inner sum brought down to Q, then all of them
-        // rotated with their key products summed into acc
-        auto qm = I.alloc((size_t)S * 2 * ln * 8), tm = I.alloc(2 * W * nn * 8);
+        // rotated with their key products summed into acc.  q holds giant i of
+        // member m at (i B + m) * 2 ln, so one ModUp serves the S B inputs
+        auto qm = I.alloc((size_t)S * B * 2 * ln * 8), tm = I.alloc((size_t)B * as * 8);
         u64 *q = static_cast<u64 *>(qm->p), *tmp = static_cast<u64 *>(tm->p);
         std::vector<u64> gs;
         for (int i = 0; i < S; ++i) {
             inner_of(*shifted[(size_t)i], tmp);
-            I.ks_moddown(tmp, ell, 2, q + (size_t)i * 2 * ln, nullptr, 0);
+            I.ks_moddown(tmp, ell, 2 * B, q + (size_t)i * B * 2 * ln, nullptr, 0);
             const u64 g = host::galois_for_rotation(I.P.logN, shifted[(size_t)i]->shift);
             if (g == 1 || !I.ks->rotkeys.count(g))
                 throw NoKeyError("rotate: no rotation key for index " + std::to_string(shifted[(size_t)i]->shift));
             gs.push_back(g);
         }
-        auto ext2 = I.modup(q + ln, ell, S, 2 * ln);
-        const size_t es = (size_t)digits * W * nn;
-        c0m = I.alloc(ln * 8);
+        auto ext2 = I.modup(q + ln, ell, S * B, 2 * ln);
+        c0m = I.alloc((size_t)B * ln * 8);
         u64 *c0 = static_cast<u64 *>(c0m->p);
         dev::KsStrides str;
-        str.ext = es;
-        str.d = 2 * ln;
+        str.ext = (size_t)B * es;
+        str.d = (size_t)B * 2 * ln;
         for (int b0 = 0; b0 < S; b0 += dev::KS_MAXKEYS) {
             const int cnt = std::min(dev::KS_MAXKEYS, S - b0);
             dev::KsKeys KK{};
@@ -1764,24 +1784,31 @@ CtPtr Engine::linear_transform_ext(const Ciphertext &x, const std::vector<long> 
                 KK.key[i] = static_cast<const u64 *>(I.ks->rotkeys.at(gs[(size_t)(b0 + i)])->p);
                 KK.perm[i] = I.perm(gs[(size_t)(b0 + i)]);
             }
-            dev::ew_permute_sum(c0, q + (size_t)b0 * 2 * ln, KK, (int)ell, cnt, b0 > 0, 2 * ln, MODS, LOGN, ST);
-            dev::ks_inner_multikey_sum(acc, static_cast<u64 *>(ext2->p) + (size_t)b0 * es, q + (size_t)b0 * 2 * ln + ln,
-                                       KK, cnt, have_acc || b0 > 0, (int)ell, I.P.K, (int)I.P.nall(), I.P.alpha,
-                                       digits, I.ext(ell), MODS, LOGN, ST, str);
+            const u64 *qb = q + (size_t)b0 * str.d, *eb = static_cast<u64 *>(ext2->p) + (size_t)b0 * str.ext;
+            if (B == 1) {
+                dev::ew_permute_sum(c0, qb, KK, (int)ell, cnt, b0 > 0, 2 * ln, MODS, LOGN, ST);
+                dev::ks_inner_multikey_sum(acc, eb, qb + ln, KK, cnt, have_acc || b0 > 0, (int)ell, I.P.K,
+                                           (int)I.P.nall(), I.P.alpha, digits, I.ext(ell), MODS, LOGN, ST, str);
+            } else {
+                dev::ew_permute_sum_members(c0, qb, KK, (int)ell, cnt, b0 > 0, str.d, B, ln, 2 * ln, MODS, LOGN, ST);
+                dev::ks_inner_multikey_sum_members(acc, eb, qb + ln, KK, cnt, have_acc || b0 > 0, (int)ell, I.P.K,
+                                                   (int)I.P.nall(), I.P.alpha, digits, B, mb, I.ext(ell), MODS, LOGN,
+                                                   ST, str);
+            }
         }
         have_acc = true;
     }
     if (!have_acc) throw std::invalid_argument("linear_transform_ext: no giants");
-    auto tm2 = I.alloc(2 * ln * 8);
+    auto tm2 = I.alloc((size_t)B * 2 * ln * 8);
     u64 *t = static_cast<u64 *>(tm2->p);
-    I.ks_moddown(acc, ell, 2, t, c0m ? static_cast<const u64 *>(c0m->p) : nullptr, 0);
-    auto r = new_ct(x.level + 1, x.slots, I.P.delta[x.level + 1], ell - 1, 1);
-    I.rescale(t, ell, ln, 2, r->data);
-    ctr.keyswitch += keyed + (size_t)S;
-    ctr.rotations += keyed + (size_t)S;
-    ctr.ptmult += npt;
-    ctr.rescale += 1;
-    count_bytes((4.0 * ell + ks_units(ell)) * (double)(keyed + (size_t)S) + 3.0 * ell * (double)npt, 1);
+    I.ks_moddown(acc, ell, 2 * B, t, c0m ? static_cast<const u64 *>(c0m->p) : nullptr, ln);
+    auto r = new_ct(x.level + 1, x.slots, I.P.delta[x.level + 1], ell - 1, B);
+    I.rescale(t, ell, ln, 2 * B, r->data);
+    ctr.keyswitch += (keyed + (size_t)S) * B;
+    ctr.rotations += (keyed + (size_t)S) * B;
+    ctr.ptmult += npt * B;
+    ctr.rescale += B;
+    count_bytes((4.0 * ell + ks_units(ell)) * (double)(keyed + (size_t)S) + 3.0 * ell * (double)npt, B);
     return r;
 }
 

@@ -64,7 +64,12 @@ struct Counters {
     // sharded runs: host wall time inside the partial-sum exchanges (header +
     // data all-reduce, from a drained stream to the reduced data), and their count
     u64 allreduce_ns = 0, allreduce_calls = 0;
+    // Bootstrapper::evalBootstrap calls and the ciphertexts they refreshed (a
+    // stack of B counts once and B times)
+    u64 boot_calls = 0, boot_cts = 0;
     Counters &operator+=(const Counters &o) {
+        boot_calls += o.boot_calls;
+        boot_cts += o.boot_cts;
         opbytes += o.opbytes;
         allreduce_ns += o.allreduce_ns;
         allreduce_calls += o.allreduce_calls;
@@ -203,6 +208,10 @@ class Engine {
     // over Q u P and multiplied there by extended plaintexts (encode_complex_ext),
     // the unrotated giant as the starting accumulator, every rotated giant brought
     // down, rotated and summed over Q u P, one final ModDown, then the rescale.
+    // Both take stacks: every member goes through the same launches (one ModUp
+    // of all members, the member-blocked key kernels of kernels.hpp, the rotated
+    // giants of all members as one key-switch input set); one ciphertext keeps
+    // the single-ciphertext launches.
     struct LtGiant {
         long shift = 0;
         std::vector<int> baby;               // indices into `baby`

@@ -163,6 +163,8 @@ _SIGS = {
     'fhe_automorph': (C.c_int, [vp, u64p, C.c_int, C.c_uint64, u64p]),
     'fhe_counters': (C.c_int, [vp, u64p]),
     'fhe_collective_stats': (C.c_int, [vp, u64p]),
+    'fhe_boot_counters': (C.c_int, [vp, u64p]),
+    'fhe_set_kway_stack': (C.c_int, [vp, C.c_int]),
     'fhe_region_marker': (C.c_int, [vp, C.c_int]),
     'fhe_set_mask_cache': (C.c_int, [vp, C.c_int]),
     'fhe_pt_limbs': (C.c_int, [vp]),
@@ -340,6 +342,8 @@ class Bootstrapper:
         return [int(x) for x in out[:m]]
 
     def bootstrap(self, x, stage=0):
+        """fhe_bootstrap_stage: 0 the whole bootstrap, 1..4 its stages; x may be a
+        stack (Context.stack) -- member m of the result equals the call on member m"""
         out = C.c_void_p()
         _chk(lib().fhe_bootstrap_stage(self.h, x.h, stage, C.byref(out)))
         return Ct(self.ctx, out.value)
@@ -750,6 +754,11 @@ class Context:
     def set_sort_lanes(self, m):
         _chk(lib().fhe_set_sort_lanes(self.h, m))
 
+    def set_kway_stack(self, on):
+        """k = 5 stages run their two compares (and the pair's bootstraps) as one
+        2-member stack (fhe_set_kway_stack); the words do not depend on it"""
+        _chk(lib().fhe_set_kway_stack(self.h, 1 if on else 0))
+
     def set_ps_split(self, split):
         """PS_SPLIT_OPENFHE (default) or PS_SPLIT_ENGINE (fhe_set_ps_split)"""
         _chk(lib().fhe_set_ps_split(self.h, int(split)))
@@ -814,6 +823,13 @@ class Context:
         out = np.zeros(2, dtype=np.uint64)
         _chk(lib().fhe_collective_stats(self.h, _u64(out)))
         return {'allreduce_s': int(out[0]) * 1e-9, 'allreduce_calls': int(out[1])}
+
+    def boot_counters(self):
+        """{'calls': bootstrap passes since reset_counters(), 'ciphertexts': the
+        ciphertexts they refreshed (a stack of B: one pass, B ciphertexts)}"""
+        out = np.zeros(2, dtype=np.uint64)
+        _chk(lib().fhe_boot_counters(self.h, _u64(out)))
+        return {'calls': int(out[0]), 'ciphertexts': int(out[1])}
 
     def region_marker(self, begin):
         """k_region_begin / k_region_end on the context stream (profiling)"""

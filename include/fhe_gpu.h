@@ -328,6 +328,14 @@ int fhe_kway_sort_boot(fhe_ctx *ctx, const fhe_ct *x, int k, int M, int dg, int 
  * storage (free both; fhe_ct_set_slots on one shows on the other); *booted = 1 / 0.
  * checkLevelAndBoot2 (:88-94) is this call on each of its two ciphertexts. */
 int fhe_check_level_and_boot(fhe_ctx *ctx, const fhe_ct *x, int need, fhe_boot *boot, int *booted, fhe_ct **out);
+/* k = 5 stages compare x against two rotations of itself.  on != 0: the pair
+ * runs as one 2-member stack on the context's engine -- one compare, its lazy
+ * bootstraps taken on the stack, and a pair that the level check has to
+ * bootstrap refreshed in one pass -- instead of two one-ciphertext chains on two
+ * lanes (fhe_set_sort_lanes is then not used by the k-way sorter).  The output
+ * words do not depend on it.  Initial value: FHE_KWAY_STACK from the environment
+ * at fhe_ctx_create, else 0. */
+int fhe_set_kway_stack(fhe_ctx *ctx, int on);
 int fhe_kway_sorter(fhe_ctx *ctx, int kk, const fhe_ct *const *x, int nx, const fhe_ct *const *cmp, int ncmp,
                     fhe_ct **out);
 /* kwaySort::sortType(k, M, stage) -> (m, logDist, slope) (src/k-way/Masking.cpp:25-48) */
@@ -369,11 +377,20 @@ int fhe_boot_rotation_indices(const fhe_boot *b, int32_t *rots, int max_rots);
 /* output level of fhe_bootstrap (levels the bootstrap consumes from the top) */
 int fhe_boot_depth(const fhe_boot *b);
 /* CryptoContext::EvalBootstrap(ct) (src/k-way/EvalUtils.cpp:76, src/sign.cpp:168):
- * x at level <= mult_depth - 1 with the setup's slots; out at fhe_boot_depth */
+ * x at level <= mult_depth - 1 with the setup's slots; out at fhe_boot_depth.
+ * x may be a stack (fhe_ct_stack) of any size: its members are refreshed in the
+ * same kernel launches, the transforms' keys and plaintexts read once per block
+ * of members, and member m of out holds, word for word, what fhe_bootstrap of
+ * member m alone gives.  The same holds for fhe_bootstrap_stage and
+ * fhe_check_level_and_boot. */
 int fhe_bootstrap(fhe_boot *b, const fhe_ct *x, fhe_ct **out);
 /* the stages alone (parity tests): 1 CoeffsToSlots of a raised ciphertext
  * (+ conjugate-add), 2 EvalMod, 3 SlotsToCoeffs, 4 ModRaise */
 int fhe_bootstrap_stage(fhe_boot *b, const fhe_ct *x, int stage, fhe_ct **out);
+/* bootstraps since the last fhe_reset_counters, over the context's engines:
+ * out[0] = bootstrap passes run, out[1] = ciphertexts refreshed (a stack of B
+ * counts as one pass and B ciphertexts) */
+int fhe_boot_counters(fhe_ctx *ctx, uint64_t out[2]);
 /* EvalConjugate-style keyed automorphism X -> X^(2n-1) */
 int fhe_conjugate(fhe_ctx *ctx, const fhe_ct *a, fhe_ct **out);
 /* keys of arbitrary galois elements g (odd, < 2n); load one generated elsewhere */
