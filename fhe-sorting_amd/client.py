@@ -11,7 +11,9 @@ that harness, in the engine's wire format (csrc/wire/wire.hpp).
               --key_rot D/key_rot.bin --input x.bin --output y.bin
 
 setup writes cc.bin, key_pub.bin, key_mult.bin, key_rot.bin (what the CLI
-loads) and key_sec.bin (kept by the client for decrypt).  Its defaults are the
+loads) and key_sec.bin (kept by the client for decrypt).  --seeded-keys writes
+the two switching-key files without their public uniform halves, as a 32-byte
+public seed the CLI expands on the GPU (half the bytes; wire kinds 7 and 8).  Its defaults are the
 reference CLI's context, src/config.json:1-9 (REFERENCE_CONFIG: ring 131072,
 multDepth 44, 40-bit scaling, batch 128, main.cpp's 21 rotations); --config
 reads another file of that format, --log-n / --depth / --scale-bits override.
@@ -110,7 +112,23 @@ def setup(a):
     if depth < need:
         raise SystemExit(f'depth {depth} < {need} needed by DirectSort<{a.n}> with CompositeSign{cfg}')
     os.makedirs(a.dir, exist_ok=True)
-    ctx = F.Context(log_n, depth, scale_bits, 60, 3, seed=a.seed, device=a.device)
+    if a.public_seed and not a.seeded_keys:
+        raise SystemExit('--public-seed is the seed of --seeded-keys')
+    if a.seeded_keys and a.seed and not a.public_seed:
+        raise SystemExit('--seeded-keys with a test --seed needs an explicit --public-seed HEX (64 hex digits): '
+                         'nothing derived from the test seed may reach a key file')
+    pub = None
+    if a.public_seed:
+        try:
+            pub = bytes.fromhex(a.public_seed)
+        except ValueError:
+            pub = b''
+        if len(pub) != 32:
+            raise SystemExit('--public-seed: 64 hex digits (32 bytes)')
+    ctx = F.Context(log_n, depth, scale_bits, 60, 3, seed=a.seed, device=a.device, keygen=not a.seeded_keys)
+    if a.seeded_keys:
+        ctx.set_public_seed(pub)
+        ctx.keygen()
     rots, added = setup_rotations(a.n, conf)
     if added:
         print(f'setup: the config\'s indexes_for_rotation_key lacks {len(added)} rotation(s) bin/fhesort uses '
@@ -118,11 +136,15 @@ def setup(a):
     ctx.gen_rotation_keys(rots)
     ctx.serialize(_path(a.dir, 'cc'))
     ctx.serialize_public_key(_path(a.dir, 'pub'))
-    ctx.serialize_eval_mult_key(_path(a.dir, 'mult'))
-    ctx.serialize_eval_automorphism_key(_path(a.dir, 'rot'))
+    if a.seeded_keys:  # half the bytes: the b halves and the public seed (wire kinds 7, 8)
+        ctx.serialize_eval_mult_key_seeded(_path(a.dir, 'mult'))
+        ctx.serialize_eval_automorphism_key_seeded(_path(a.dir, 'rot'))
+    else:
+        ctx.serialize_eval_mult_key(_path(a.dir, 'mult'))
+        ctx.serialize_eval_automorphism_key(_path(a.dir, 'rot'))
     ctx.serialize_secret_key(_path(a.dir, 'sec'))
     print(f'setup: ring 2^{log_n}, depth {depth}, scale 2^{scale_bits}, sign {cfg}, '
-          f'{len(rots)} rotations -> {a.dir}')
+          f'{len(rots)} rotations{", seeded keys" if a.seeded_keys else ""} -> {a.dir}')
     ctx.close()
 
 
@@ -182,6 +204,12 @@ def main(argv=None):
             s.add_argument('--depth', type=int, default=0, help='override mult_depth')
             s.add_argument('--seed', type=int, default=0,
                            help='0 (default): keys from the OS CSPRNG; nonzero: reproducible keys, for tests only')
+            s.add_argument('--seeded-keys', action='store_true',
+                           help='write key_mult.bin / key_rot.bin without their uniform halves (half the bytes); '
+                                'bin/fhesort expands them on the GPU')
+            s.add_argument('--public-seed', default=None, metavar='HEX',
+                           help='the 32-byte public seed of --seeded-keys (default: from the OS CSPRNG; '
+                                'required with --seed)')
         elif name == 'encrypt':
             g = s.add_mutually_exclusive_group(required=True)
             g.add_argument('--values')

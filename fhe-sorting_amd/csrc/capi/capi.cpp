@@ -1,7 +1,9 @@
 // extern "C" boundary of the MI355X engine (declarations: include/fhe_gpu.h).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
+#include <sys/random.h>
 
+#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -150,6 +152,57 @@ int fhe_ctx_load_keys(fhe_ctx *ctx, const uint64_t *relin, const int32_t *rot_id
     return guard([&] {
         if (relin) ctx->eng->load_relin(relin);
         for (int i = 0; i < nrot; ++i) ctx->eng->load_rotation(rot_idx[i], rot_keys[i]);
+    });
+}
+int fhe_set_public_seed(fhe_ctx *ctx, const uint8_t seed[32]) {
+    return guard([&] {
+        NEED(ctx);
+        if (seed) {
+            ctx->eng->set_public_seed(seed);
+            return;
+        }
+        // a test context's streams all derive from its seed: nothing drawn here may
+        // stand in for an explicit public seed there
+        if (ctx->params.seed != 0)
+            throw std::invalid_argument("fhe_set_public_seed: a context with a test seed needs an explicit public seed");
+        uint8_t s[32];
+        size_t got = 0;
+        while (got < sizeof s) {
+            const ssize_t r = getrandom(s + got, sizeof s - got, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                throw std::runtime_error("getrandom failed: cannot draw a public seed");
+            }
+            got += (size_t)r;
+        }
+        ctx->eng->set_public_seed(s);
+    });
+}
+int fhe_get_public_seed(fhe_ctx *ctx, uint8_t seed[32]) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(seed);
+        if (!ctx->eng->get_public_seed(seed)) throw std::invalid_argument("fhe_get_public_seed: no public seed set");
+    });
+}
+int fhe_key_is_seeded(fhe_ctx *ctx, uint64_t galois) {
+    int r = -FHE_EINVAL;
+    const int st = guard([&] {
+        NEED(ctx);
+        r = ctx->eng->key_seeded(galois);
+        if (r < 0) {
+            g_err = "fhe_key_is_seeded: no such key";
+            r = -FHE_ENOKEY;
+        }
+    });
+    return st == FHE_OK ? r : -st;
+}
+int fhe_public_poly(fhe_ctx *ctx, const uint8_t seed[32], uint64_t kid, int digit, uint64_t *out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(seed);
+        NEED(out);
+        ctx->eng->public_poly(seed, kid, digit, out);
     });
 }
 uint64_t fhe_key_bytes(fhe_ctx *ctx) { return ctx ? ctx->eng->key_bytes() : 0; }
@@ -1121,6 +1174,8 @@ WIRE_KEY(fhe_deserialize_secret_key, wire::load_secret_key)
 WIRE_KEY(fhe_serialize_eval_mult_key, wire::save_eval_mult_key)
 WIRE_KEY(fhe_deserialize_eval_mult_key, wire::load_eval_mult_key)
 WIRE_KEY(fhe_serialize_eval_automorphism_key, wire::save_automorphism_keys)
+WIRE_KEY(fhe_serialize_eval_mult_key_seeded, wire::save_eval_mult_key_seeded)
+WIRE_KEY(fhe_serialize_eval_automorphism_key_seeded, wire::save_automorphism_keys_seeded)
 #undef WIRE_KEY
 int fhe_deserialize_eval_automorphism_key(fhe_ctx *ctx, const char *path, int *count) {
     return guard([&] {

@@ -1039,6 +1039,87 @@ __global__ __launch_bounds__(NT) void k_signed_to_rns(u64 *out, const int64_t *c
     }
     out[(size_t)l * n + k] = r;
 }
+// Public stream v1 (csrc/wire/wire.hpp): the uniform half of one switching-key
+// digit, out[l][k] for every prime l, regenerated from the public seed.  A thread
+// owns one ChaCha20 block = 8 coefficients of one limb (q and its bit length are
+// uniform per block) and retries its rejected coefficients with the blocks of the
+// next attempts itself -- a prime just above a power of two rejects half its
+// candidates, so most threads take several.  Its 64 bytes would leave a wave
+// storing at a 64-byte lane stride, so the block's 16 KiB go through LDS and come
+// out as 16 contiguous bytes per lane, 1 KiB per wave store.
+// grid: x = ceil(n / 8 / NT), y = limb
+__device__ __forceinline__ void chacha_quarter(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) {
+    a += b, d ^= a, d = __builtin_rotateleft32(d, 16);
+    c += d, b ^= c, b = __builtin_rotateleft32(b, 12);
+    a += b, d ^= a, d = __builtin_rotateleft32(d, 8);
+    c += d, b ^= c, b = __builtin_rotateleft32(b, 7);
+}
+struct PublicKeyWords {
+    uint32_t w[8];
+};
+__global__ __launch_bounds__(NT) void k_expand_uniform(u64 *out, PublicKeyWords key, uint32_t kid, uint32_t digit,
+                                                       const Mod *mods, int logN, uint32_t *err) {
+    __shared__ u64 stage[NT * 8];
+    const uint32_t groups = 1u << (logN - 3);  // ChaCha blocks per limb and attempt
+    const uint32_t l = blockIdx.y;
+    const uint32_t g = blockIdx.x * NT + threadIdx.x;
+    const u64 q = mods[l].q;
+    const int shift = 64 - mods[l].k;
+    // LDS slot of this thread's coefficient pair p: pairs rotate with the thread
+    // so the wave's 8-byte writes spread over the banks
+    const uint32_t sw = (threadIdx.x >> 2) & 3;
+    if (g < groups) {
+        u64 r[8] = {};
+        uint32_t pending = 0xff;
+        for (uint32_t t = 0; t < 64 && pending; ++t) {
+            uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u,
+                              key.w[0],    key.w[1],    key.w[2],    key.w[3],
+                              key.w[4],    key.w[5],    key.w[6],    key.w[7],
+                              t * groups + g, kid,      digit | (l << 16), 0x41454846u};
+            uint32_t x[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[i] = s[i];
+#pragma unroll
+            for (int rd = 0; rd < 10; ++rd) {
+                chacha_quarter(x[0], x[4], x[8], x[12]);
+                chacha_quarter(x[1], x[5], x[9], x[13]);
+                chacha_quarter(x[2], x[6], x[10], x[14]);
+                chacha_quarter(x[3], x[7], x[11], x[15]);
+                chacha_quarter(x[0], x[5], x[10], x[15]);
+                chacha_quarter(x[1], x[6], x[11], x[12]);
+                chacha_quarter(x[2], x[7], x[8], x[13]);
+                chacha_quarter(x[3], x[4], x[9], x[14]);
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const u64 cand = ((u64)(x[2 * c] + s[2 * c]) | ((u64)(x[2 * c + 1] + s[2 * c + 1]) << 32)) >> shift;
+                const bool take = (pending >> c & 1) && cand < q;
+                r[c] = take ? cand : r[c];
+                pending &= ~((uint32_t)take << c);
+            }
+        }
+        if (pending) atomicOr(err, 1u);  // 64 attempts exhausted: the host reports FHE_EINTERNAL
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            u64 *d = stage + threadIdx.x * 8 + 2 * ((uint32_t)p ^ sw);
+            d[0] = r[2 * p];
+            d[1] = r[2 * p + 1];
+        }
+    }
+    __syncthreads();
+    // 16-byte chunk c of the block's output: pair c & 3 of thread c >> 2
+    u64 *o = out + ((size_t)l << logN) + (size_t)blockIdx.x * NT * 8;
+    const uint32_t live = min((uint32_t)NT, groups - blockIdx.x * NT) * 4;  // chunks this block owns
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+        const uint32_t c = pass * NT + threadIdx.x;
+        if (c >= live) break;
+        const uint32_t th = c >> 2;
+        const ulonglong2 v =
+            *reinterpret_cast<const ulonglong2 *>(stage + th * 8 + 2 * ((c & 3) ^ ((th >> 2) & 3)));
+        *reinterpret_cast<ulonglong2 *>(o + 2 * (size_t)c) = v;
+    }
+}
 // ModRaise: out[z][l][k] = centred(in[z][k] mod q_src) mod q_l  (in: coefficient form,
 // values in [0, 2 q_src); the centred lift of x > q_src / 2 is x - q_src)
 __global__ __launch_bounds__(NT) void k_lift_centered(u64 *out, const u64 *in, size_t seg_in, size_t seg_out,
@@ -2654,6 +2735,18 @@ void ew_signed_to_rns(u64 *out, const int64_t *coef, int limbs, const int *pmap,
     if (limbs <= 0 || members <= 0) return;
     hipLaunchKernelGGL(k_signed_to_rns, pt_grid(logN, limbs, members), dim3(NT), 0, st, out, coef, pmap, mods, logN,
                        out_stride, coef_stride);
+}
+void expand_uniform(u64 *out, const uint32_t key[8], uint32_t kid, int digit, int limbs, const Mod *mods, int logN,
+                    uint32_t *err, hipStream_t st) {
+    if (limbs <= 0) return;
+    if (logN < 3 || limbs > 0xffff || digit < 0 || digit > 0xffff)
+        throw std::invalid_argument("expand_uniform: digit / limb index beyond the stream's 16-bit nonce fields");
+    PublicKeyWords K;
+    for (int i = 0; i < 8; ++i) K.w[i] = key[i];
+    const size_t groups = (size_t)1 << (logN - 3);
+    const dim3 grid((unsigned)((groups + NT - 1) / NT), (unsigned)limbs);
+    note_launch("k_expand_uniform", grid, dim3(NT));
+    hipLaunchKernelGGL(k_expand_uniform, grid, dim3(NT), 0, st, out, K, kid, (uint32_t)digit, mods, logN, err);
 }
 void ew_lift_centered(u64 *out, const u64 *in, int src, int limbs, int segs, size_t seg_in, size_t seg_out,
                       const Mod *mods, int logN, hipStream_t st) {

@@ -235,6 +235,11 @@ void ew_c0_op(u64 *out, const u64 *a, const u64 *p, int64_t K, int sh, int mode,
               const Mod *mods, int logN, hipStream_t st);
 void ew_signed_to_rns(u64 *out, const int64_t *coef, int limbs, const int *pmap, const Mod *mods, int logN,
                       hipStream_t st, int members = 1, size_t out_stride = 0, size_t coef_stride = 0);
+// public stream v1 (csrc/wire/wire.hpp): out [limbs][n] = the uniform half of digit
+// `digit` of switching key `kid` under the public seed's eight key words, limb l
+// over prime l; *err |= 1 if a coefficient exhausts its 64 attempts
+void expand_uniform(u64 *out, const uint32_t key[8], uint32_t kid, int digit, int limbs, const Mod *mods, int logN,
+                    uint32_t *err, hipStream_t st);
 
 // ------------------------------------------------------------ device encode
 // (encode.hip) special inverse FFT of B members of S slots in place (v [B][S]),

@@ -203,7 +203,15 @@ struct Engine::Impl {
     struct KeySet {
         std::shared_ptr<DevMem> s_ntt, pk, relin;
         std::map<u64, std::shared_ptr<DevMem>> rotkeys;
+        // public stream v1 (csrc/wire/wire.hpp): the seed keygen expands the
+        // switching keys' uniform halves from, when set, and the seed of every
+        // key whose a halves are that stream (kid 0 = relin, else the galois
+        // element); a key loaded in full is in no entry
+        bool has_pub_seed = false;
+        PublicSeed pub_seed{};
+        std::map<u64, PublicSeed> seeded;
     };
+    std::shared_ptr<DevMem> pub_err;  // the expansion kernel's error word
     std::shared_ptr<KeySet> ks = std::make_shared<KeySet>();
     std::map<u64, std::shared_ptr<DevMem>> perms;
     int key_digits = 0;
@@ -811,6 +819,39 @@ void Engine::keygen() {
     HIP_OK(hipStreamSynchronize(I.st));
 }
 
+// ---- public stream v1: the switching keys' uniform halves from a public seed
+namespace {
+// enqueue the expansion of a_digit of key `kid` into out [nall][n]
+void expand_public(Engine::Impl &I, const PublicSeed &seed, u64 kid, int digit, u64 *out) {
+    if (!I.pub_err) {
+        I.pub_err = I.alloc(sizeof(uint32_t));
+        HIP_OK(hipMemsetAsync(I.pub_err->p, 0, sizeof(uint32_t), I.st));
+    }
+    uint32_t key[8];
+    host::public_seed_key(seed.data(), key);
+    dev::expand_uniform(out, key, (uint32_t)kid, digit, (int)I.P.nall(), I.mods, I.P.logN,
+                        static_cast<uint32_t *>(I.pub_err->p), I.st);
+}
+// after the expansions of key `kid`: drains the stream and throws if a
+// coefficient exhausted its attempts (the host stream names the digit)
+void check_expansion(Engine::Impl &I, const PublicSeed &seed, u64 kid) {
+    if (!I.pub_err) return;
+    uint32_t err = 0;
+    HIP_OK(hipMemcpyAsync(&err, I.pub_err->p, sizeof err, hipMemcpyDeviceToHost, I.st));
+    HIP_OK(hipStreamSynchronize(I.st));
+    if (!err) return;
+    HIP_OK(hipMemsetAsync(I.pub_err->p, 0, sizeof(uint32_t), I.st));
+    std::vector<u64> a(I.P.nall() * I.n());
+    int bad = -1;
+    for (int j = 0; j < I.key_digits && bad < 0; ++j)
+        if (!host::public_stream_v1(seed.data(), kid, j, I.P.primes.data(), 0, I.P.nall(), I.n(), a.data())) bad = j;
+    throw std::runtime_error("public stream v1: a coefficient of key " + std::to_string(kid) +
+                             (bad >= 0 ? ", digit " + std::to_string(bad) : std::string()) +
+                             " found no candidate below its prime in " + std::to_string(host::kPublicAttempts) +
+                             " attempts");
+}
+}  // namespace
+
 void gen_switch_key_impl(Engine::Impl &I, const u64 *sp, u64 kid, u64 *out) {
     const size_t n = I.n(), nall = I.P.nall(), nq = I.P.nq();
     const u64 *S = static_cast<const u64 *>(I.ks->s_ntt->p);
@@ -823,17 +864,22 @@ void gen_switch_key_impl(Engine::Impl &I, const u64 *sp, u64 kid, u64 *out) {
         for (int k = 0; k < I.P.K; ++k) acc = host::mulmod(acc, I.P.primes[nq + k] % mi.q, mi);
         Pmod[i] = (int64_t)acc;
     }
-    // sample every digit's (a_j, e_j) on host threads, then combine on the GPU
+    // sample every digit's (a_j, e_j) on host threads, then combine on the GPU;
+    // under a public seed a_j is expanded on the device instead (public stream v1)
+    const bool seeded = I.ks->has_pub_seed;
+    const PublicSeed pub = I.ks->pub_seed;
     std::vector<std::vector<u64>> A(digits);
     std::vector<std::vector<int64_t>> E(digits);
     {
         std::vector<std::thread> th;
         for (int j = 0; j < digits; ++j)
             th.emplace_back([&, j]() {
-                host::Prng ga(I.ent, host::tags::swk_a(kid, j), true);
-                A[j].resize(nall * n);
-                for (size_t l = 0; l < nall; ++l)
-                    for (size_t k = 0; k < n; ++k) A[j][l * n + k] = host::sample_uniform_mod(ga, I.P.primes[l]);
+                if (!seeded) {
+                    host::Prng ga(I.ent, host::tags::swk_a(kid, j), true);
+                    A[j].resize(nall * n);
+                    for (size_t l = 0; l < nall; ++l)
+                        for (size_t k = 0; k < n; ++k) A[j][l * n + k] = host::sample_uniform_mod(ga, I.P.primes[l]);
+                }
                 host::Prng ge(I.ent, host::tags::swk_e(kid, j));
                 E[j].resize(n);
                 for (size_t k = 0; k < n; ++k) E[j][k] = host::sample_cbd(ge);
@@ -846,7 +892,10 @@ void gen_switch_key_impl(Engine::Impl &I, const u64 *sp, u64 kid, u64 *out) {
     for (int j = 0; j < digits; ++j) {
         u64 *bj = out + ((size_t)j * 2 + 0) * nall * n;
         u64 *aj = out + ((size_t)j * 2 + 1) * nall * n;
-        HIP_OK(hipMemcpyAsync(aj, A[j].data(), nall * n * 8, hipMemcpyHostToDevice, I.st));
+        if (seeded)
+            expand_public(I, pub, kid, j, aj);
+        else
+            HIP_OK(hipMemcpyAsync(aj, A[j].data(), nall * n * 8, hipMemcpyHostToDevice, I.st));
         HIP_OK(hipMemcpyAsync(ec->p, E[j].data(), n * 8, hipMemcpyHostToDevice, I.st));
         dev::ew_signed_to_rns(bj, static_cast<int64_t *>(ec->p), (int)nall, nullptr, I.mods, I.P.logN, I.st);
         dev::ntt_forward(bj, (int)nall, 1, 0, nullptr, I.T, I.st);
@@ -857,6 +906,12 @@ void gen_switch_key_impl(Engine::Impl &I, const u64 *sp, u64 kid, u64 *out) {
         for (size_t i = lo; i < hi; ++i) W.w[i - lo] = (u64)Pmod[i];
         dev::ew_add_scaled(bj + lo * n, sp + lo * n, W, (int)(hi - lo), dev::Seg{0, 0, 0}, I.mods + lo, I.P.logN, I.st);
         HIP_OK(hipStreamSynchronize(I.st));  // host buffers A[j], E[j] go out of scope after the loop
+    }
+    if (seeded) {
+        check_expansion(I, pub, kid);
+        I.ks->seeded[kid] = pub;
+    } else {
+        I.ks->seeded.erase(kid);
     }
 }
 
@@ -910,6 +965,7 @@ void Engine::load_relin(const u64 *key) {
     const size_t bytes = (size_t)I.key_digits * 2 * I.P.nall() * I.n() * 8;
     I.ks->relin = I.alloc(bytes);
     HIP_OK(hipMemcpy(I.ks->relin->p, key, bytes, hipMemcpyHostToDevice));
+    I.ks->seeded.erase(0);
 }
 void Engine::load_rotation(long k, const u64 *key) {
     auto &I = *impl;
@@ -919,6 +975,7 @@ void Engine::load_rotation(long k, const u64 *key) {
     auto m = I.alloc(bytes);
     HIP_OK(hipMemcpy(m->p, key, bytes, hipMemcpyHostToDevice));
     I.ks->rotkeys[g] = m;
+    I.ks->seeded.erase(g);
 }
 void Engine::load_galois(u64 g, const u64 *key) {
     auto &I = *impl;
@@ -927,6 +984,62 @@ void Engine::load_galois(u64 g, const u64 *key) {
     auto m = I.alloc(bytes);
     HIP_OK(hipMemcpy(m->p, key, bytes, hipMemcpyHostToDevice));
     I.ks->rotkeys[g] = m;
+    I.ks->seeded.erase(g);
+}
+// a seeded key: the b halves [digits][nall][n] from the host, the a halves
+// expanded on the device
+namespace {
+std::shared_ptr<DevMem> load_seeded_key(Engine::Impl &I, const PublicSeed &seed, u64 kid, const u64 *b) {
+    drain_before_key_load();
+    const size_t half = I.P.nall() * I.n();
+    auto m = I.alloc((size_t)I.key_digits * 2 * half * 8);
+    u64 *key = static_cast<u64 *>(m->p);
+    HIP_OK(hipMemcpy2D(key, 2 * half * 8, b, half * 8, half * 8, (size_t)I.key_digits, hipMemcpyHostToDevice));
+    for (int j = 0; j < I.key_digits; ++j) expand_public(I, seed, kid, j, key + ((size_t)j * 2 + 1) * half);
+    check_expansion(I, seed, kid);
+    return m;
+}
+}  // namespace
+void Engine::load_relin_seeded(const uint8_t seed[32], const u64 *b) {
+    PublicSeed s;
+    std::memcpy(s.data(), seed, 32);
+    impl->ks->relin = load_seeded_key(*impl, s, 0, b);
+    impl->ks->seeded[0] = s;
+}
+void Engine::load_galois_seeded(const uint8_t seed[32], u64 g, const u64 *b) {
+    PublicSeed s;
+    std::memcpy(s.data(), seed, 32);
+    impl->ks->rotkeys[g] = load_seeded_key(*impl, s, g, b);
+    impl->ks->seeded[g] = s;
+}
+void Engine::set_public_seed(const uint8_t seed[32]) {
+    std::memcpy(impl->ks->pub_seed.data(), seed, 32);
+    impl->ks->has_pub_seed = true;
+}
+bool Engine::get_public_seed(uint8_t seed[32]) const {
+    if (!impl->ks->has_pub_seed) return false;
+    std::memcpy(seed, impl->ks->pub_seed.data(), 32);
+    return true;
+}
+int Engine::key_seeded(u64 kid, uint8_t *seed) const {
+    const auto &K = *impl->ks;
+    if (kid == 0 ? !K.relin : !K.rotkeys.count(kid)) return -1;
+    auto it = K.seeded.find(kid);
+    if (it == K.seeded.end()) return 0;
+    if (seed) std::memcpy(seed, it->second.data(), 32);
+    return 1;
+}
+void Engine::public_poly(const uint8_t seed[32], u64 kid, int digit, u64 *out) {
+    auto &I = *impl;
+    if (digit < 0 || digit >= I.key_digits) throw std::invalid_argument("public_poly: digit out of range");
+    if (kid >> 32) throw std::invalid_argument("public_poly: key id beyond 32 bits");
+    PublicSeed s;
+    std::memcpy(s.data(), seed, 32);
+    const size_t words = I.P.nall() * I.n();
+    auto m = I.alloc(words * 8);
+    expand_public(I, s, kid, digit, static_cast<u64 *>(m->p));
+    check_expansion(I, s, kid);
+    HIP_OK(hipMemcpy(out, m->p, words * 8, hipMemcpyDeviceToHost));
 }
 bool Engine::has_galois_key(u64 g) const { return impl->ks->rotkeys.count(g) > 0; }
 bool Engine::has_rotation_key(long k) const {
@@ -956,6 +1069,21 @@ void Engine::export_galois(u64 g, u64 *out) {
     auto it = impl->ks->rotkeys.find(g);
     if (it == impl->ks->rotkeys.end()) throw std::invalid_argument("export: no key for galois element " + std::to_string(g));
     export_key(*impl, it->second, switch_key_words(), out, "galois key");
+}
+namespace {
+// the b halves [digits][nall][n] of a switching key
+void export_key_b(Engine::Impl &I, const std::shared_ptr<DevMem> &m, u64 *out, const char *what) {
+    if (!m) throw std::invalid_argument(std::string("export: no ") + what);
+    const size_t half = I.P.nall() * I.n();
+    HIP_OK(hipStreamSynchronize(I.st));
+    HIP_OK(hipMemcpy2D(out, half * 8, m->p, 2 * half * 8, half * 8, (size_t)I.key_digits, hipMemcpyDeviceToHost));
+}
+}  // namespace
+void Engine::export_relin_b(u64 *out) { export_key_b(*impl, impl->ks->relin, out, "relinearisation key"); }
+void Engine::export_galois_b(u64 g, u64 *out) {
+    auto it = impl->ks->rotkeys.find(g);
+    if (it == impl->ks->rotkeys.end()) throw std::invalid_argument("export: no key for galois element " + std::to_string(g));
+    export_key_b(*impl, it->second, out, "galois key");
 }
 size_t Engine::key_bytes() const {
     size_t b = impl->ks->relin ? impl->ks->relin->bytes : 0;
@@ -2323,6 +2451,13 @@ void Engine::time_kernel(const std::string &name, size_t ell, int iters, double 
                                I.LT.modup_fp_off[ell].data(), I.LT.modup_fp_mid);
         };
         bytes = (double)mem * (ell + (size_t)digits * W - ell) * B;
+    } else if (name == "expand_uniform") {  // one digit's uniform half over all nq + K primes
+        auto bm = I.alloc(I.P.nall() * nn * 8);
+        u64 *a = static_cast<u64 *>(bm->p);
+        em = bm;  // keep alive
+        const PublicSeed seed{};
+        launch = [&, a, seed] { expand_public(I, seed, 0, 0, a); };
+        bytes = (double)I.P.nall() * B;  // written
     } else {
         throw std::invalid_argument("time_kernel: unknown kernel " + name);
     }

@@ -12,6 +12,7 @@
 // EvalFastRotation/EvalChebyshevSeriesPS, called from src/sign.cpp,
 // src/comparison.cpp, src/rotation.h and src/sort_algo.h).
 #pragma once
+#include <array>
 #include <complex>
 #include <cstddef>
 #include <cstdint>
@@ -26,6 +27,7 @@ namespace fhe {
 
 using u64 = uint64_t;
 using i64 = int64_t;
+using PublicSeed = std::array<uint8_t, 32>;  // public stream v1 (csrc/wire/wire.hpp)
 
 struct DevMem;  // pooled device allocation (engine.hip)
 
@@ -135,6 +137,22 @@ class Engine {
     void export_relin(u64 *out);
     std::vector<u64> galois_elements() const;     // ascending
     void export_galois(u64 g, u64 *out);
+    // Seeded switching keys (public stream v1, csrc/wire/wire.hpp).  With a public
+    // seed set, the keys generated afterwards take their uniform halves a_j from
+    // the seed's stream, expanded on the device, and are recorded as seeded; a
+    // key loaded in full is not.  key_seeded: 1 (seed, if given, receives the
+    // key's seed) / 0 / -1 no such key; kid 0 = relinearisation key, else the
+    // galois element.
+    void set_public_seed(const uint8_t seed[32]);
+    bool get_public_seed(uint8_t seed[32]) const;
+    int key_seeded(u64 kid, uint8_t *seed = nullptr) const;
+    // a_digit of key `kid` under `seed` over all nq + K primes, [nall][n] to host
+    void public_poly(const uint8_t seed[32], u64 kid, int digit, u64 *out);
+    // the b halves alone, [digits][nall][n]; the loads expand the a halves
+    void export_relin_b(u64 *out);
+    void export_galois_b(u64 g, u64 *out);
+    void load_relin_seeded(const uint8_t seed[32], const u64 *b);
+    void load_galois_seeded(const uint8_t seed[32], u64 g, const u64 *b);
 
     // ------------------------------------------------- encode / encrypt ---
     PtPtr encode(const std::vector<double> &v, int slots, int level);

@@ -439,6 +439,45 @@ Entropy Entropy::from_seed(u64 seed) {
 Prng::Prng(const Entropy &e, u64 tag, bool pub)
     : use_cc(e.secure && !pub), sm(e.secure ? e.seed_a : e.seed, tag), cc(e.key, tag) {}
 
+void public_seed_key(const uint8_t seed[32], uint32_t key[8]) {
+    for (int i = 0; i < 8; ++i)
+        key[i] = (uint32_t)seed[4 * i] | ((uint32_t)seed[4 * i + 1] << 8) | ((uint32_t)seed[4 * i + 2] << 16) |
+                 ((uint32_t)seed[4 * i + 3] << 24);
+}
+bool public_stream_v1(const uint8_t seed[32], u64 kid, int digit, const u64 *primes, size_t first, size_t limbs,
+                      size_t n, u64 *out) {
+    uint32_t key[8];
+    public_seed_key(seed, key);
+    bool ok = true;
+    for (size_t i = 0; i < limbs; ++i) {
+        const size_t l = first + i;
+        const u64 q = primes[l];
+        const int shift = __builtin_clzll(q);  // 64 - bits(q)
+        const uint32_t nonce[3] = {(uint32_t)kid, (uint32_t)digit | ((uint32_t)l << 16), kPublicNonce};
+        for (size_t g = 0; g < n / 8; ++g) {
+            unsigned pending = 0xff;
+            for (int t = 0; t < kPublicAttempts && pending; ++t) {
+                uint32_t w[16];
+                chacha20_block(key, (uint32_t)((size_t)t * (n / 8) + g), nonce, w);
+                for (int c = 0; c < 8; ++c) {
+                    if (!(pending >> c & 1)) continue;
+                    const u64 cand = ((u64)w[2 * c] | ((u64)w[2 * c + 1] << 32)) >> shift;
+                    if (cand < q) {
+                        out[i * n + 8 * g + c] = cand;
+                        pending &= ~(1u << c);
+                    }
+                }
+            }
+            if (pending) {
+                for (int c = 0; c < 8; ++c)
+                    if (pending >> c & 1) out[i * n + 8 * g + c] = 0;
+                ok = false;
+            }
+        }
+    }
+    return ok;
+}
+
 // ---------------------------------------------- fp64 sums of products --
 // One target row of an fp64 basis conversion (kernels.hip k_moddown_rescale_fp).
 // The kernel feeds source k as two exact doubles with y_k = yh 2^30 + yl + off_k,

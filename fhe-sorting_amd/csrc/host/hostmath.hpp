@@ -133,6 +133,17 @@ int sample_cbd(G &g) {
     const u64 a = g.next(), b = g.next();
     return __builtin_popcountll(a & m) - __builtin_popcountll(b & m);
 }
+// Public stream v1 (definition: csrc/wire/wire.hpp): the uniform half a_digit of
+// switching key `kid` under a 32-byte public seed, limbs first..first+limbs-1 of
+// `primes`, [limbs][n] in evaluation form.  Counter-based, so the device kernel
+// (kernels.hip k_expand_uniform) regenerates the same words in parallel.  Returns
+// false if a coefficient found no candidate below its prime in kPublicAttempts.
+constexpr int kPublicAttempts = 64;
+constexpr uint32_t kPublicNonce = 0x41454846u;  // "FHEA"
+void public_seed_key(const uint8_t seed[32], uint32_t key[8]);  // eight little-endian u32
+bool public_stream_v1(const uint8_t seed[32], u64 kid, int digit, const u64 *primes, size_t first, size_t limbs,
+                      size_t n, u64 *out);
+
 namespace tags {
 constexpr u64 secret = 1, pk_a = 2, pk_e = 3;
 inline u64 swk_a(u64 kid, int j) { return 0x100000ULL + kid * 16 + 2 * (u64)j; }

@@ -234,7 +234,89 @@ void check_residues(const uint64_t *w, size_t limbs, size_t n, const std::vector
 void check_switch_key(const uint64_t *w, const host::Params &P, int digits, const std::string &path) {
     for (int j = 0; j < 2 * digits; ++j) check_residues(w + (size_t)j * P.nall() * P.n, P.nall(), P.n, P.primes, 0, path);
 }
+// the b halves of a switching key, [digits][nall][n]
+void check_switch_key_b(const uint64_t *w, const host::Params &P, int digits, const std::string &path) {
+    for (int j = 0; j < digits; ++j) check_residues(w + (size_t)j * P.nall() * P.n, P.nall(), P.n, P.primes, 0, path);
+}
 uint64_t pid_of(const Engine &e, const CtxParams &p) { return params_id(p, e.params().primes); }
+
+// the seed words of a seeded file: the 32 seed bytes as four little-endian u64
+void seed_words(const PublicSeed &s, uint64_t w[4]) {
+    for (int i = 0; i < 4; ++i) {
+        w[i] = 0;
+        for (int b = 0; b < 8; ++b) w[i] |= (uint64_t)s[8 * i + b] << (8 * b);
+    }
+}
+PublicSeed seed_of(const uint64_t w[4]) {
+    PublicSeed s;
+    for (int i = 0; i < 4; ++i)
+        for (int b = 0; b < 8; ++b) s[8 * i + b] = (uint8_t)(w[i] >> (8 * b));
+    return s;
+}
+std::string key_label(uint64_t kid) {
+    return kid ? "the key of galois element " + std::to_string(kid) : std::string("the eval-mult key");
+}
+// the seed of key `kid`, which a seeded file can only hold if the key is seeded
+PublicSeed seed_for_writing(const Engine &e, uint64_t kid) {
+    PublicSeed s;
+    const int st = e.key_seeded(kid, s.data());
+    if (st < 0) throw std::invalid_argument("serialize: no " + key_label(kid).substr(4));
+    if (st == 0)
+        throw std::invalid_argument("serialize: " + key_label(kid) +
+                                    " is not seeded (it was loaded in full or generated without a public seed), so "
+                                    "a seeded file cannot hold it");
+    return s;
+}
+// stream version and seed words that follow a seeded body's first word
+PublicSeed read_stream_header(Reader &r) {
+    const uint64_t v = r.word();
+    if (v != kPublicStreamVersion)
+        throw std::invalid_argument(r.path() + ": public stream version " + std::to_string(v) + " (this build expands " +
+                                    std::to_string(kPublicStreamVersion) + ")");
+    uint64_t w[4];
+    r.get(w, 4);
+    return seed_of(w);
+}
+void load_eval_mult_key_seeded(Engine &e, const CtxParams &p, Reader &r) {
+    const auto &P = e.params();
+    r.expect(EvalMultKeySeeded, pid_of(e, p), P);
+    if (r.word() != (uint64_t)e.key_digits()) throw std::invalid_argument(r.path() + ": key digit count differs");
+    const PublicSeed seed = read_stream_header(r);
+    std::vector<uint64_t> b(e.switch_key_words() / 2);
+    r.get(b.data(), b.size());
+    r.done();
+    check_switch_key_b(b.data(), P, e.key_digits(), r.path());
+    e.load_relin_seeded(seed.data(), b.data());
+}
+int load_automorphism_keys_seeded(Engine &e, const CtxParams &p, Reader &r) {
+    const auto &P = e.params();
+    r.expect(AutomorphismSeeded, pid_of(e, p), P);
+    const uint64_t count = r.word();
+    const size_t bw = e.switch_key_words() / 2;
+    // the digit count is implied by the body size
+    if (count > r.info.body_words || r.info.body_words != 6 + count * (1 + bw))
+        throw IoError(r.path() + ": key count, digit count and body size disagree");
+    const PublicSeed seed = read_stream_header(r);
+    // validate every key before installing any
+    std::vector<uint64_t> b(bw);
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            r.rewind();
+            for (int i = 0; i < 6; ++i) r.word();
+        }
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint64_t g = r.word();
+            if (!(g & 1) || g >= 2 * P.n) throw std::invalid_argument(r.path() + ": bad galois element " + std::to_string(g));
+            r.get(b.data(), bw);
+            if (pass == 0)
+                check_switch_key_b(b.data(), P, e.key_digits(), r.path());
+            else
+                e.load_galois_seeded(seed.data(), g, b.data());
+        }
+    }
+    r.done();
+    return (int)count;
+}
 }  // namespace
 
 void Checksum::update(const uint64_t *w, size_t count) {
@@ -285,6 +367,8 @@ const char *kind_name(uint32_t kind) {
     case Automorphism: return "eval-automorphism key set";
     case CiphertextK: return "ciphertext";
     case SecretKey: return "secret key";
+    case EvalMultKeySeeded: return "seeded eval-mult key";
+    case AutomorphismSeeded: return "seeded eval-automorphism key set";
     default: return "unknown object";
     }
 }
@@ -385,6 +469,7 @@ void save_eval_mult_key(Engine &e, const CtxParams &p, const std::string &path) 
 void load_eval_mult_key(Engine &e, const CtxParams &p, const std::string &path) {
     const auto &P = e.params();
     Reader r(path);
+    if (r.info.kind == EvalMultKeySeeded) return load_eval_mult_key_seeded(e, p, r);
     r.expect(EvalMultKey, pid_of(e, p), P);
     if (r.word() != (uint64_t)e.key_digits()) throw std::invalid_argument(path + ": key digit count differs");
     std::vector<uint64_t> k(e.switch_key_words());
@@ -392,6 +477,45 @@ void load_eval_mult_key(Engine &e, const CtxParams &p, const std::string &path) 
     r.done();
     check_switch_key(k.data(), P, e.key_digits(), path);
     e.load_relin(k.data());
+}
+void save_eval_mult_key_seeded(Engine &e, const CtxParams &p, const std::string &path) {
+    const auto &P = e.params();
+    const PublicSeed seed = seed_for_writing(e, 0);
+    std::vector<uint64_t> b(e.switch_key_words() / 2);
+    e.export_relin_b(b.data());
+    Writer w(path, EvalMultKeySeeded, pid_of(e, p), P, 6 + b.size());
+    uint64_t sw[4];
+    seed_words(seed, sw);
+    w.word((uint64_t)e.key_digits());
+    w.word(kPublicStreamVersion);
+    w.body(sw, 4);
+    w.body(b.data(), b.size());
+    w.finish();
+}
+void save_automorphism_keys_seeded(Engine &e, const CtxParams &p, const std::string &path) {
+    const auto &P = e.params();
+    const auto gs = e.galois_elements();
+    if (gs.empty()) throw std::invalid_argument("serialize: no galois keys to write");
+    // every key must be seeded, all with one seed: checked before the file is opened
+    const PublicSeed seed = seed_for_writing(e, gs[0]);
+    for (uint64_t g : gs)
+        if (seed_for_writing(e, g) != seed)
+            throw std::invalid_argument("serialize: " + key_label(g) + " was generated under another public seed than " +
+                                        key_label(gs[0]) + "; a seeded file holds one seed");
+    const size_t bw = e.switch_key_words() / 2;
+    Writer w(path, AutomorphismSeeded, pid_of(e, p), P, 6 + gs.size() * (1 + bw));
+    uint64_t sw[4];
+    seed_words(seed, sw);
+    w.word(gs.size());
+    w.word(kPublicStreamVersion);
+    w.body(sw, 4);
+    std::vector<uint64_t> b(bw);
+    for (uint64_t g : gs) {
+        e.export_galois_b(g, b.data());
+        w.word(g);
+        w.body(b.data(), bw);
+    }
+    w.finish();
 }
 void save_automorphism_keys(Engine &e, const CtxParams &p, const std::string &path) {
     const auto &P = e.params();
@@ -411,6 +535,7 @@ void save_automorphism_keys(Engine &e, const CtxParams &p, const std::string &pa
 int load_automorphism_keys(Engine &e, const CtxParams &p, const std::string &path) {
     const auto &P = e.params();
     Reader r(path);
+    if (r.info.kind == AutomorphismSeeded) return load_automorphism_keys_seeded(e, p, r);
     r.expect(Automorphism, pid_of(e, p), P);
     if (r.word() != (uint64_t)e.key_digits()) throw std::invalid_argument(path + ": key digit count differs");
     const uint64_t count = r.word();

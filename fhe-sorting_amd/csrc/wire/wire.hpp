@@ -22,6 +22,30 @@
 //   kind 4 automorphism   count, then count x (galois element, [digits][2][nall][n])
 //   kind 5 ciphertext     level, slots, limbs, batch (1), scale (f64 bits), [2][limbs][n]
 //   kind 6 secret key     [nall][n]
+//   kind 7 seeded eval-mult key    digits, 1 (stream version), seed[4],
+//                         [digits][nall][n] (the b halves only)
+//   kind 8 seeded automorphism     count, 1 (stream version), seed[4], then
+//                         count x (galois element, [digits][nall][n])
+//
+// Seeded keys (kinds 7, 8).  Half of a switching key is the public uniform
+// polynomial a_j, which carries nothing beyond the seed of the generator that
+// drew it: a seeded file ships the b halves and a 32-byte public seed (four
+// little-endian u64), and the reader regenerates every a_j on the device.  Only
+// keys generated under a public seed (fhe_set_public_seed) can be written this
+// way; all keys of one file share one seed.
+//
+// Public stream v1.  ChaCha20, RFC 8439 §2.3 block function.
+//   key      the 32 seed bytes read as eight little-endian u32
+//   indices  switching key kid (0: relinearisation, else the galois element g),
+//            digit j, prime index l in 0..nall-1, coefficient k in 0..n-1,
+//            attempt t = 0, 1, ...; a is sampled directly in evaluation form
+//   nonce    { (u32)kid, j | (l << 16), 0x41454846 ("FHEA") }
+//   counter  t (n/8) + (k >> 3)
+//   candidate  (w[2(k&7)] | w[2(k&7)+1] << 32) >> (64 - bits(q_l)) over the
+//            block's 16 output words w, bits(q) the bit length of q
+//   a_j[l][k] is the first candidate below q_l.  Attempts are capped at 64: a
+//   coefficient without a candidate by then fails the call (FHE_EINTERNAL; at
+//   worst a prime rejects half its candidates, so the chance is 2^-64 per word).
 //
 // Every polynomial is in the engine's evaluation (NTT) form, residues < q_i,
 // little-endian.  params_id hashes (log_n, mult_depth, scale_bits, first_bits,
@@ -39,8 +63,18 @@
 namespace fhe {
 namespace wire {
 
-enum Kind : uint32_t { Context = 1, PublicKey = 2, EvalMultKey = 3, Automorphism = 4, CiphertextK = 5, SecretKey = 6 };
+enum Kind : uint32_t {
+    Context = 1,
+    PublicKey = 2,
+    EvalMultKey = 3,
+    Automorphism = 4,
+    CiphertextK = 5,
+    SecretKey = 6,
+    EvalMultKeySeeded = 7,
+    AutomorphismSeeded = 8
+};
 constexpr uint32_t kVersion = 1;
+constexpr uint64_t kPublicStreamVersion = 1;
 constexpr uint64_t kMagic = 0x5754524f53454846ull;  // "FHESORTW"
 
 // raised on file-system failures and malformed / corrupted files
@@ -91,6 +125,11 @@ void load_eval_mult_key(Engine &e, const CtxParams &p, const std::string &path);
 void save_automorphism_keys(Engine &e, const CtxParams &p, const std::string &path);
 // returns the number of keys loaded
 int load_automorphism_keys(Engine &e, const CtxParams &p, const std::string &path);
+// kinds 7 / 8: std::invalid_argument naming the key if a key to be written is
+// not seeded or the keys do not share one seed.  The loaders above read either
+// kind, going by the file's header.
+void save_eval_mult_key_seeded(Engine &e, const CtxParams &p, const std::string &path);
+void save_automorphism_keys_seeded(Engine &e, const CtxParams &p, const std::string &path);
 void save_ciphertext(Engine &e, const CtxParams &p, const Ciphertext &ct, const std::string &path);
 CtPtr load_ciphertext(Engine &e, const CtxParams &p, const std::string &path);
 

@@ -205,6 +205,12 @@ _SIGS = {
     **{f'fhe_{d}serialize_{k}': (C.c_int, [vp, C.c_char_p])
        for d in ('', 'de') for k in ('public_key', 'secret_key', 'eval_mult_key')},
     'fhe_serialize_eval_automorphism_key': (C.c_int, [vp, C.c_char_p]),
+    'fhe_serialize_eval_mult_key_seeded': (C.c_int, [vp, C.c_char_p]),
+    'fhe_serialize_eval_automorphism_key_seeded': (C.c_int, [vp, C.c_char_p]),
+    'fhe_set_public_seed': (C.c_int, [vp, C.c_char_p]),
+    'fhe_get_public_seed': (C.c_int, [vp, C.c_char_p]),
+    'fhe_key_is_seeded': (C.c_int, [vp, C.c_uint64]),
+    'fhe_public_poly': (C.c_int, [vp, C.c_char_p, C.c_uint64, C.c_int, u64p]),
 }
 
 
@@ -214,7 +220,7 @@ class WireInfo(C.Structure):
 
 
 WIRE_KINDS = {1: 'context', 2: 'public_key', 3: 'eval_mult_key', 4: 'eval_automorphism_key', 5: 'ciphertext',
-              6: 'secret_key'}
+              6: 'secret_key', 7: 'eval_mult_key_seeded', 8: 'eval_automorphism_key_seeded'}
 
 
 def set_mfma_sums(mask):
@@ -463,6 +469,14 @@ class Context:
         _chk(lib().fhe_deserialize_eval_automorphism_key(self.h, os.fsencode(path), C.byref(n)))
         return n.value
 
+    # seeded switching keys (public stream v1, csrc/wire/wire.hpp): the b halves and
+    # the public seed; the deserialize calls above read either format
+    def serialize_eval_mult_key_seeded(self, path):
+        _chk(lib().fhe_serialize_eval_mult_key_seeded(self.h, os.fsencode(path)))
+
+    def serialize_eval_automorphism_key_seeded(self, path):
+        _chk(lib().fhe_serialize_eval_automorphism_key_seeded(self.h, os.fsencode(path)))
+
     def serialize_ciphertext(self, ct, path):
         _chk(lib().fhe_serialize_ciphertext(self.h, ct.h, os.fsencode(path)))
 
@@ -531,6 +545,37 @@ class Context:
 
     def key_bytes(self):
         return lib().fhe_key_bytes(self.h)
+
+    def set_public_seed(self, seed=None):
+        """Keys generated afterwards take their uniform halves from public stream v1
+        under `seed` (32 bytes; None: drawn from the OS CSPRNG, refused on a
+        context with a test seed)."""
+        if seed is not None:
+            seed = bytes(seed)
+            if len(seed) != 32:
+                raise ValueError('a public seed is 32 bytes')
+        _chk(lib().fhe_set_public_seed(self.h, seed))
+
+    def get_public_seed(self):
+        buf = C.create_string_buffer(32)
+        _chk(lib().fhe_get_public_seed(self.h, buf))
+        return buf.raw
+
+    def key_is_seeded(self, galois=0):
+        """1 / 0 for the key of galois element `galois` (0: the eval-mult key)."""
+        r = lib().fhe_key_is_seeded(self.h, int(galois))
+        if r < 0:
+            _chk(-r)
+        return r
+
+    def public_poly(self, seed, kid, digit):
+        """a_digit of switching key `kid` under `seed`, [nq + K][n] (kernel parity)."""
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError('a public seed is 32 bytes')
+        out = np.empty((self.nq + self.K, self.n), dtype=np.uint64)
+        _chk(lib().fhe_public_poly(self.h, seed, int(kid), int(digit), _u64(out)))
+        return out
 
     def encode_complex(self, v, slots, level, scale=None):
         v = np.asarray(v, dtype=np.complex128)

@@ -84,6 +84,20 @@ int fhe_ctx_load_public(fhe_ctx *ctx, const uint64_t *pk);
 int fhe_ctx_load_keys(fhe_ctx *ctx, const uint64_t *relin, const int32_t *rot_idx,
                       const uint64_t *const *rot_keys, int nrot);
 uint64_t fhe_key_bytes(fhe_ctx *ctx);
+/* Seeded switching keys.  Half of every switching key is the public uniform
+ * polynomial a_j; under a public seed keygen expands it on the GPU from a
+ * counter-based ChaCha20 stream ("public stream v1", csrc/wire/wire.hpp) instead
+ * of sampling it on the host, and the key can be written without that half
+ * (fhe_serialize_eval_*_key_seeded below).  The secret, the errors and the
+ * public key do not depend on it; without a public seed every key is what it
+ * was before. */
+/* public seed of the switching keys' uniform halves; NULL draws one from the OS CSPRNG,
+   allowed only on a secure context (params.seed == 0): a test context must be given an
+   explicit seed so nothing derived from the test seed can reach a file (else FHE_EINVAL).
+   Affects keys generated afterwards. */
+int fhe_set_public_seed(fhe_ctx *ctx, const uint8_t seed[32]);
+int fhe_get_public_seed(fhe_ctx *ctx, uint8_t seed[32]);          /* FHE_EINVAL if none */
+int fhe_key_is_seeded(fhe_ctx *ctx, uint64_t galois /* 0 = eval-mult */);  /* 1 / 0, < 0 no such key */
 
 /* ------------------------------------------------------ ciphertext / pt */
 /* Encryption::encryptInput = MakeCKKSPackedPlaintext + Encrypt (src/encryption.cpp:5-12) */
@@ -414,6 +428,8 @@ int fhe_ntt(fhe_ctx *ctx, uint64_t *host, int prime_index, int limbs, int invers
 int fhe_modup(fhe_ctx *ctx, const uint64_t *d, int ell, uint64_t *ext);
 int fhe_moddown(fhe_ctx *ctx, const uint64_t *in, int ell, uint64_t *out);
 int fhe_automorph(fhe_ctx *ctx, const uint64_t *in, int limbs, uint64_t galois, uint64_t *out);
+/* kernel-level parity: a_digit of key `kid` over all nq+K primes, [nall][n] to host */
+int fhe_public_poly(fhe_ctx *ctx, const uint8_t seed[32], uint64_t kid, int digit, uint64_t *out);
 /* Device-memory variants (SURVEY §8(b) fhe_ntt_fwd/inv, fhe_automorph): the
  * limbs are device pointers, the work is enqueued on `stream` (a hipStream_t;
  * NULL = the context stream) and the call returns without synchronising.
@@ -486,7 +502,8 @@ int fhe_kernel_clock_stop(fhe_ctx *ctx, char *json, size_t cap, size_t *needed);
  * is loaded.  Errors: FHE_EIO (open / read / write / corrupt / not a wire file),
  * FHE_EINVAL (wrong object kind, other context, out-of-range residues). */
 typedef struct {
-    uint32_t kind;     /* 1 context, 2 public key, 3 eval-mult key, 4 automorphism keys, 5 ciphertext, 6 secret key */
+    uint32_t kind;     /* 1 context, 2 public key, 3 eval-mult key, 4 automorphism keys, 5 ciphertext, 6 secret key,
+                          7 seeded eval-mult key, 8 seeded automorphism keys */
     uint32_t version;
     uint64_t params_id, log_n, nq, K, body_words;
 } fhe_wire_info;
@@ -507,6 +524,13 @@ int fhe_deserialize_eval_mult_key(fhe_ctx *ctx, const char *path);
  * every galois key of the context (rotations, conjugation); count: keys loaded */
 int fhe_serialize_eval_automorphism_key(fhe_ctx *ctx, const char *path);
 int fhe_deserialize_eval_automorphism_key(fhe_ctx *ctx, const char *path, int *count);
+/* the same keys without their uniform halves (wire kinds 7 and 8: the b halves and the
+ * public seed, half the bytes): FHE_EINVAL, naming the key, unless every key to be
+ * written was generated under a public seed and all under the same one.  The two
+ * deserialize calls above read either format, going by the file's header, and expand
+ * the uniform halves on the GPU. */
+int fhe_serialize_eval_mult_key_seeded(fhe_ctx *ctx, const char *path);
+int fhe_serialize_eval_automorphism_key_seeded(fhe_ctx *ctx, const char *path);
 /* Serial::{Deserialize,Serialize}ToFile of a ciphertext (src/sort.h:69-73, 97-102) */
 int fhe_serialize_ciphertext(fhe_ctx *ctx, const fhe_ct *ct, const char *path);
 int fhe_deserialize_ciphertext(fhe_ctx *ctx, const char *path, fhe_ct **out);
