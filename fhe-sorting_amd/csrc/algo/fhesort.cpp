@@ -1276,7 +1276,7 @@ struct AlgoPhase {
     ~AlgoPhase() { Engine::set_algo_phase(prev); }
 };
 
-void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots) {
+void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots, int batch) {
     // a single rank reduces only when the caller gave it a collective (an
     // RCCL communicator of world 1 still runs the all-reduce)
     if (!sh.allreduce) {
@@ -1284,7 +1284,9 @@ void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots) {
         return;
     }
     checkShardWorld(cc.params(), sh.world);
-    if (acc && acc->batch != 1) throw std::invalid_argument("sharded run: a partial must be a single ciphertext");
+    if (acc && acc->batch != batch)
+        throw std::invalid_argument(batch == 1 ? "sharded run: a partial must be a single ciphertext"
+                                               : "sharded run: a partial stack differs from the expected members");
     // header: presence, level + 1, (level + 1)^2, limbs -- summed over ranks.
     // Every rank sees the same sums, so every rank takes the same branch below.
     // The exchange's time (bench.py: allreduce_ms beside rank_compute_ms) runs
@@ -1304,9 +1306,9 @@ void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots) {
     sh.allreduce(hdr.ptr, 4);
     cc.d2h(h, hdr.ptr, 4);
     const ShardHeader H = checkShardHeader(h);
-    if (!acc) acc = cc.zero_like(H.level, slots);
+    if (!acc) acc = cc.zero_like(H.level, slots, batch);
     if (acc->limbs != H.limbs) throw std::runtime_error("sharded run: partial limb count differs from the header");
-    sh.allreduce(acc->data, 2 * acc->limbs * cc.n());
+    sh.allreduce(acc->data, 2 * (size_t)batch * acc->limbs * cc.n());
     cc.reduce_after_allreduce(*acc);
     if (timed) {
         cc.sync();
@@ -1315,12 +1317,12 @@ void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots) {
     }
     cc.ctr.allreduce_calls += 1;
 }
-void DirectSortN::reducePartial(CtPtr &acc, int slots) {
+void DirectSortN::reducePartial(CtPtr &acc, int slots, int batch) {
     Shard sh;
     sh.rank = shard_rank;
     sh.world = shard_world;
     sh.allreduce = allreduce;
-    fhe::reducePartial(cc, sh, acc, slots);
+    fhe::reducePartial(cc, sh, acc, slots, batch);
 }
 
 // The np baby-step rotations x, rot(x,1), ..., rot(x,np-1) of vecRotsOpt
@@ -1516,6 +1518,158 @@ CtPtr DirectSortN::rotationIndexCheckN(const Ciphertext &rank, const Ciphertext 
         out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
     out->slots = N;
     return out;
+}
+
+int DirectSortN::indexSeriesLevel(int rank_level) const {
+    std::vector<double> c(sincCoefficients());
+    trim_zeros(c);
+    // the 1/2N scaling, then the series (evalChebyshevSeriesPS)
+    return rank_level + 1 + chebPSDepthSplit((int)c.size() - 1, cc.ps_split());
+}
+
+namespace {
+// the ciphertexts as one stack: a view when they already are consecutive
+// members of one allocation (rotateMembers' output when every member took one
+// keyed step), else a stacked copy
+CtPtr asStack(Engine &E, const std::vector<CtPtr> &v) {
+    const size_t words = 2 * v[0]->limbs * E.n();
+    bool consecutive = true;
+    for (size_t m = 0; m < v.size(); ++m)
+        consecutive = consecutive && v[m]->batch == 1 && v[m]->mem == v[0]->mem && v[m]->data == v[0]->data + m * words;
+    if (consecutive) {
+        auto r = std::make_shared<Ciphertext>(*v[0]);
+        r->batch = (int)v.size();
+        return r;
+    }
+    std::vector<const Ciphertext *> p;
+    for (auto &x : v) p.push_back(x.get());
+    return E.stack(p);
+}
+}  // namespace
+
+void DirectSortN::blindRotationColumns(Lane L, const std::vector<CtPtr> &mi, int num_slots, int np,
+                                       const std::vector<int> &ibs, int P, int num_partition, CtPtr &acc) {
+    Engine &E = *L.eng;
+    for (int i = 0; i < (num_slots / N) / np; ++i) {
+        std::vector<const Ciphertext *> cs;
+        std::vector<const Plaintext *> ps;
+        for (int j = 0; j < np; ++j) {
+            cs.push_back(mi[j].get());
+            ps.push_back(&mask(E, 0, num_slots, np * i + j, j, mi[j]->level));
+        }
+        CtPtr tmp = E.mul_plain_sum(cs, ps);  // src/sort_algo.h:573-577, every column and batch at once
+        // the giant steps: the batch's own amount, repeated per column
+        std::vector<int> rots;
+        bool any = false;
+        for (int p = 0; p < P; ++p)
+            for (size_t m = 0; m < ibs.size(); ++m) {
+                rots.push_back(ibs[m] * num_partition + i * np);
+                any = any || rots.back() % tmp->slots != 0;
+            }
+        CtPtr rotated = any ? asStack(E, L.rot->rotateMembers(*tmp, rots)) : tmp;
+        E.sum_member_groups(*rotated, P, acc);  // the sum mod q does not depend on the order of the terms
+    }
+}
+
+// rotationIndexCheckN for P columns.  The difference stack, its scaling and the
+// doubled-sinc series are the single-column path's own calls, run once per
+// chunk; the column enters at the product, so every member of the column stack
+// holds the words rotationIndexCheckN computes for (that batch, that column),
+// and all later sums are exact mod q.
+std::vector<CtPtr> DirectSortN::rotationIndexCheckColumns(const Ciphertext &rank,
+                                                          const std::vector<const Ciphertext *> &cols) {
+    const SortShape s = checkShape(N, max_batch);
+    const int P = (int)cols.size();
+    if (P < 1) throw std::invalid_argument("sort columns: no columns");
+    const int series_level = indexSeriesLevel(rank.level);
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("sort columns: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1)
+            throw std::invalid_argument("sort columns: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->level > series_level)
+            throw std::runtime_error("sort columns: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the series output (level " +
+                                     std::to_string(series_level) + "): no levels left to meet it");
+    }
+    std::vector<double> idx(N);
+    for (int i = 0; i < N; ++i) idx[i] = (double)i;
+    PtPtr idxpt = cc.encode(idx, N, rank.level);
+    CtPtr imr = cc.plain_sub(*idxpt, rank);
+    imr->slots = s.num_slots;
+    // every column brought once to the level the product meets it at (mul's own
+    // level_adjust of its broadcast operand, so the same words)
+    std::vector<CtPtr> xs(P);
+    for (int p = 0; p < P; ++p) {
+        xs[p] = cc.level_adjust(*cols[p], series_level);
+        xs[p]->slots = s.num_slots;
+    }
+    const std::vector<double> &coeffs = sincCoefficients();
+    std::vector<int> ridx(s.np);
+    for (int i = 0; i < s.np; ++i) ridx[i] = i;
+    std::vector<int> mine;
+    for (int b = 0; b < s.num_batch; ++b)
+        if (b % shard_world == shard_rank) mine.push_back(b);
+    cc.sync();  // imr and the columns are read by every lane
+    const size_t chunk = (size_t)std::max(1, max_stack);
+    // columns per stacked product: the member bound over the largest chunk any
+    // lane stacks (run_lanes gives a lane at most ceil(batches / lanes) of them)
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
+    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph("index_batches");
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<const Plaintext *> chks;
+            std::vector<int> ibs;
+            for (size_t i = c0; i < std::min(bs.size(), c0 + chunk); ++i) {
+                const int b = bs[i];
+                chks.push_back(&mask(E, 1, s.num_slots, b * s.num_partition, 0, imr->level));
+                ibs.push_back(b);
+            }
+            CtPtr r = E.mul_const(*(chks.size() == 1 ? E.sub_plain(*imr, *chks[0]) : E.sub_plain_stacked(*imr, chks)),
+                                  1.0 / N / 2);
+            r = evalChebyshevSeriesPS(E, *r, coeffs, -1.0, 1.0);
+            if (r->level != series_level) throw std::logic_error("sort columns: unexpected series output level");
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<const Ciphertext *> group;
+                for (int p = p0; p < p0 + Pg; ++p) group.push_back(xs[p].get());
+                CtPtr masked = E.mul_columns(*r, group);  // member (p - p0) B + z
+                std::vector<CtPtr> mi = L.rot->rotateMany(*masked, ridx);
+                masked.reset();
+                blindRotationColumns(L, mi, s.num_slots, s.np, ibs, Pg, s.num_partition, accs[g]);
+            }
+        }
+        if (bs.empty()) return nullptr;
+        if (accs.size() == 1) return accs[0];
+        std::vector<const Ciphertext *> all;
+        for (auto &a : accs) all.push_back(a.get());
+        return E.stack(all);  // the column groups, in column order
+    });
+    CtPtr out;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(out, *p);
+    cc.sync();
+    parts.clear();
+    reducePartial(out, s.num_slots, P);
+    AlgoPhase ph("index_fold");
+    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+        out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
+    std::vector<CtPtr> outs(P);
+    for (int p = 0; p < P; ++p) {
+        outs[p] = P == 1 ? out : cc.clone(*cc.member(*out, p));
+        outs[p]->slots = N;
+    }
+    return outs;
+}
+
+std::vector<CtPtr> DirectSortN::sortColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
+                                            SignFunc f, const SignConfig &cfg) {
+    if (!cache_masks) refresh_masks();
+    CtPtr rank = constructRank(key, f, cfg);
+    return rotationIndexCheckColumns(*rank, cols);
 }
 
 // Re-encodes every cached mask (the reference's per-use encoding,

@@ -194,8 +194,10 @@ struct Shard {
 // hold no partial agree on the level and contribute a zero ciphertext, and
 // ranks whose partials disagree on level or limbs all fail with the same error
 // instead of entering mismatched collectives; then the limbs are summed as u64
-// and reduced mod q.  No-op for one rank.
-void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots);
+// and reduced mod q.  No-op for one rank.  A partial may be a stack of `batch`
+// members (the same on every rank): one header, then all members' words in one
+// all-reduce.
+void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots, int batch = 1);
 
 // The u64 sum of `world` residues, each < q_max, must not wrap: world * q_max
 // < 2^64 (world <= 16 for the 60-bit first prime).  Throws otherwise.
@@ -212,6 +214,23 @@ class DirectSortN {
     CtPtr constructRank(const Ciphertext &x, SignFunc f, const SignConfig &cfg);
     CtPtr rotationIndexCheckN(const Ciphertext &rank, const Ciphertext &x);
     CtPtr sort(const Ciphertext &x, SignFunc f, const SignConfig &cfg);
+    // Records: out[p] = rotationIndexCheckN(rank, *cols[p]) word for word, with the
+    // doubled-sinc series (which depends on the rank alone) evaluated once per
+    // batch chunk and multiplied into every column in one stacked product
+    // (Engine::mul_columns); the masked sums, giant steps, lane partials, the
+    // shard reduction and the fold then run on column stacks.  A column deeper
+    // than the series output (indexSeriesLevel) is refused before any work.
+    // With tied keys the columns mix exactly as the key does (tests/tie_model.py).
+    std::vector<CtPtr> rotationIndexCheckColumns(const Ciphertext &rank, const std::vector<const Ciphertext *> &cols);
+    // constructRank(key), then rotationIndexCheckColumns
+    std::vector<CtPtr> sortColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols, SignFunc f,
+                                   const SignConfig &cfg);
+    // level of the index check's series output for a rank at rank_level: where
+    // the product meets the column
+    int indexSeriesLevel(int rank_level) const;
+    // most members (columns x stacked batches) of one stacked column product;
+    // more columns run in groups.  Results do not depend on it.
+    int max_col_members = 64;
     // sort_hybrid (src/sort_algo.h:1050-1064): constructRank, then the MEHP24-style
     // matrix index check rotationIndexCheckHybrid (:893-1047); its num_batch^2
     // masks run stacked, blocks b shard over ranks like the rank-sort batches
@@ -257,7 +276,12 @@ class DirectSortN {
     // blindRotationOptN over a stacked `masked` (member m belongs to batch ibs[m]), summed over members
     CtPtr blindRotationStacked(Lane L, const std::vector<CtPtr> &masked, int num_slots, int np,
                                const std::vector<int> &ibs, int num_partition);
-    void reducePartial(CtPtr &acc, int slots);
+    // blindRotationStacked over P column groups: `masked` holds P * ibs.size()
+    // members, column-major; the rotated members are summed per column into the
+    // P-member stack acc (one grouped-sum launch per giant step)
+    void blindRotationColumns(Lane L, const std::vector<CtPtr> &masked, int num_slots, int np,
+                              const std::vector<int> &ibs, int P, int num_partition, CtPtr &acc);
+    void reducePartial(CtPtr &acc, int slots, int batch = 1);
     std::vector<CtPtr> babySteps(const Ciphertext &x, int np);
     // encoded on the calling lane's engine, published once complete (thread-safe)
     const Plaintext &mask(Engine &E, int kind, int num_slots, int k, int rot, int level);

@@ -31,6 +31,7 @@ struct fhe_ctx {
     std::map<std::pair<int, std::vector<int>>, std::unique_ptr<DirectSortN>> sorters;
     int sort_stack = 32;
     int sort_lanes = 2;
+    int sort_col_members = 256;  // fhe_set_sort_column_members (initial value: FHE_SORT_COLS_MEMBERS)
     bool mask_cache = true;  // fhe_set_mask_cache
     std::unique_ptr<Engine> kway_lane;  // the k-way sorter's second lane (forked on first use)
     bool kway_stack = false;            // fhe_set_kway_stack (initial value: FHE_KWAY_STACK)
@@ -113,6 +114,7 @@ int fhe_ctx_create(const fhe_params *p, int device, fhe_ctx **out) {
                                           p->seed);
         c->params = wire::CtxParams{p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum, p->seed};
         if (const char *e = std::getenv("FHE_KWAY_STACK")) c->kway_stack = std::atoi(e) != 0;
+        if (const char *e = std::getenv("FHE_SORT_COLS_MEMBERS")) c->sort_col_members = std::max(1, std::atoi(e));
         *out = c.release();
     });
 }
@@ -556,6 +558,69 @@ int fhe_direct_sort(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
     });
 }
 
+int fhe_direct_sort_columns(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols, int ncols,
+                            int N, const int32_t *rots, int nrot, int n, int dg, int df, int shard_rank,
+                            int shard_world, fhe_allreduce_fn fn, void *user, fhe_ct **outs) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(outs);
+        if (!key && !rank) throw std::invalid_argument("fhe_direct_sort_columns: neither a key nor a rank given");
+        if (ncols < 1 || !cols) throw std::invalid_argument("fhe_direct_sort_columns: ncols must be >= 1");
+        const Ciphertext &packing = rank ? *rank->p : *key->p;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            const std::string which = "fhe_direct_sort_columns: column " + std::to_string(p);
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
+            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (cols[p]->p->slots != packing.slots)
+                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the " +
+                                            (rank ? "rank " : "key ") + std::to_string(packing.slots));
+            v.push_back(cols[p]->p.get());
+        }
+        CtAllReduce reduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = shard_rank;
+        ds.shard_world = shard_world;
+        ds.allreduce = std::move(reduce);
+        // the depth refusal (a column below the series output) is raised by the
+        // index check before it starts any work
+        std::vector<CtPtr> r = rank ? ds.rotationIndexCheckColumns(*rank->p, v)
+                                    : ds.sortColumns(*key->p, v, SignFunc::CompositeSign, cfgof(n, dg, df));
+        for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
+    });
+}
+int fhe_mul_columns(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *cols, int ncols, fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(out_stack);
+        if (ncols < 1 || !cols) throw std::invalid_argument("fhe_mul_columns: ncols must be >= 1");
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            if (!cols[p]) throw std::invalid_argument("fhe_mul_columns: column " + std::to_string(p) + " is null");
+            v.push_back(cols[p]->p.get());
+        }
+        *out_stack = wrap(ctx->eng->mul_columns(*a->p, v));
+    });
+}
+int fhe_ct_sum_member_groups(fhe_ctx *ctx, const fhe_ct *a, int groups, fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(out_stack);
+        CtPtr acc;
+        ctx->eng->sum_member_groups(*a->p, groups, acc);
+        *out_stack = wrap(acc);
+    });
+}
+
 int fhe_sort_hybrid(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, const int32_t *rots, int nrot, int n,
                     int dg, int df, int mode, int max_array, int mask_mode, int shard_rank, int shard_world,
                     fhe_allreduce_fn fn, void *user, fhe_ct **out) {
@@ -927,6 +992,14 @@ int fhe_set_sort_lanes(fhe_ctx *ctx, int lanes) {
         NEED(ctx);
         if (lanes < 1 || lanes > 8) throw std::invalid_argument("lanes must be in 1..8");
         ctx->sort_lanes = lanes;
+    });
+}
+
+int fhe_set_sort_column_members(fhe_ctx *ctx, int max_members) {
+    return guard([&] {
+        NEED(ctx);
+        if (max_members < 1) throw std::invalid_argument("max_members must be >= 1");
+        ctx->sort_col_members = max_members;
     });
 }
 

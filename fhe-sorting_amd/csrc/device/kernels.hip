@@ -302,6 +302,79 @@ __global__ __launch_bounds__(NT) void k_sum_members(u64 *out, const u64 *in, int
     }
     st2(out + o, make_ulonglong2(r0, r1));
 }
+// k_tensor of the stack a (members at stride sa) against P single ciphertexts
+// (the columns of a record sort, all at a's level): grid z = group * members + z;
+// a thread loads member z's (a0, a1) once and forms the tensor against the up
+// to PC columns of its group, every column's loads issued ahead of the
+// arithmetic.  Output member p * members + z (column-major), each the words
+// k_tensor gives on (member z, column p).  The last group is guarded.
+constexpr int TC_MAX = 32;  // columns of one launch
+constexpr int TC_PC = 4;    // columns per thread
+struct TensorCols {
+    const u64 *b[TC_MAX];
+    int P;
+};
+template <int PC>
+__global__ __launch_bounds__(NT) void k_tensor_cols(u64 *d01, u64 *d2, const u64 *a, size_t ln_all, size_t sa,
+                                                    TensorCols C, int members, const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod m = mods[l];
+    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
+    const size_t o = (size_t)l * n + k;
+    const u64 *A = a + (size_t)z * sa;
+    const ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
+    ulonglong2 b0[PC], b1[PC];
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < C.P) {
+            const u64 *Bp = C.b[p0 + j];
+            b0[j] = ld2(Bp + o);
+            b1[j] = ld2(Bp + ln_all + o);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < C.P) {
+            ulonglong2 e0, e1, e2;
+            e0.x = mul_barrett(a0.x, b0[j].x, m);
+            e0.y = mul_barrett(a0.y, b0[j].y, m);
+            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
+            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
+            e2.x = mul_barrett(a1.x, b1[j].x, m);
+            e2.y = mul_barrett(a1.y, b1[j].y, m);
+            const size_t mo = (size_t)(p0 + j) * members + z;
+            st2(d01 + mo * 2 * ln_all + o, e0);
+            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
+            st2(d2 + mo * ln_all + o, e2);
+        }
+    }
+}
+// out [groups][2][limbs][n] (+)= sum over the B members of each group of
+// in [groups * B][2][limbs][n] (group p = members p B .. p B + B - 1): grid
+// z = 2 group + poly.  k_sum_members' sum, member by member; accumulate adds
+// the group's sum to what out holds instead of replacing it.
+__global__ __launch_bounds__(NT) void k_sum_member_groups(u64 *out, const u64 *in, int per_group, int accumulate,
+                                                          size_t ln_all, const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t g = blockIdx.z >> 1, poly = blockIdx.z & 1;
+    const size_t lo = (size_t)l * n + k, oo = (size_t)blockIdx.z * ln_all + lo;
+    ulonglong2 prev = make_ulonglong2(0, 0);
+    if (accumulate) prev = ld2(out + oo);
+    u64 r0 = 0, r1 = 0;
+    for (int m = 0; m < per_group; ++m) {
+        const ulonglong2 x = ld2(in + ((g * per_group + m) * 2 + poly) * ln_all + lo);
+        r0 = add_mod(r0, x.x, q);
+        r1 = add_mod(r1, x.y, q);
+    }
+    st2(out + oo, make_ulonglong2(add_mod(prev.x, r0, q), add_mod(prev.y, r1, q)));
+}
 constexpr int LIN_MAX = 32;
 struct LinArgs {
     const u64 *x[LIN_MAX];
@@ -2574,6 +2647,30 @@ void ew_sum_members(u64 *out, const u64 *in, int members, int limbs, const Mod *
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
     hipLaunchKernelGGL(k_sum_members, ew_grid(logN, limbs, 2), dim3(NT), 0, st, out, in, members, ln_all, mods, logN);
+}
+int tensor_cols_per_thread() { return TC_PC; }
+void ew_tensor_cols(u64 *d01, u64 *d2, const u64 *a, const u64 *const *cols, int P, int limbs, int members, size_t sa,
+                    const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0 || P <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < P; base += TC_MAX) {
+        TensorCols C{};
+        C.P = std::min(TC_MAX, P - base);
+        for (int i = 0; i < C.P; ++i) C.b[i] = cols[base + i];
+        const int groups = (C.P + TC_PC - 1) / TC_PC;
+        const double B = 8.0 * (2.0 * members * groups + 2.0 * C.P + 3.0 * C.P * members) * ln_all;
+        const size_t mo = (size_t)base * members;  // first output member of this launch
+        launch_clocked(inst_name<TC_PC>("k_tensor_cols"), B, k_tensor_cols<TC_PC>, ew_grid(logN, limbs, members * groups),
+                       dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, ln_all, sa, C, members, mods, logN);
+    }
+}
+void ew_sum_member_groups(u64 *out, const u64 *in, int groups, int per_group, int limbs, bool accumulate,
+                          const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || groups <= 0 || per_group <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    const double B = 8.0 * (2.0 * groups * per_group + (accumulate ? 4.0 : 2.0) * groups) * ln_all;
+    launch_clocked("k_sum_member_groups", B, k_sum_member_groups, ew_grid(logN, limbs, 2 * groups), dim3(NT), st, out,
+                   in, per_group, accumulate ? 1 : 0, ln_all, mods, logN);
 }
 void ew_linear_sum(u64 *out, const u64 *const *xs, const int64_t *K, int m, int limbs, int segs, size_t seg,
                    size_t xseg, const Mod *mods, int logN, hipStream_t st, bool accumulate, const uint8_t *sh) {

@@ -204,6 +204,16 @@ bool ew_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int
                    int logN, hipStream_t st, const u64 *a2 = nullptr, size_t sa2 = 0);
 // out [2][limbs][n] = sum_m in [m][2][limbs][n]
 void ew_sum_members(u64 *out, const u64 *in, int members, int limbs, const Mod *mods, int logN, hipStream_t st);
+// ew_tensor of a's `members` members (stride sa) against each of P single
+// ciphertexts cols[p] ([2][limbs][n]) in one pass: member p * members + z of
+// d01 / d2 holds the tensor of (member z, column p), word for word ew_tensor's.
+// a is loaded once per tensor_cols_per_thread() columns.
+int tensor_cols_per_thread();
+void ew_tensor_cols(u64 *d01, u64 *d2, const u64 *a, const u64 *const *cols, int P, int limbs, int members, size_t sa,
+                    const Mod *mods, int logN, hipStream_t st);
+// out [groups][2][limbs][n] (+)= sum_z in [p * per_group + z] for every group p, one launch
+void ew_sum_member_groups(u64 *out, const u64 *in, int groups, int per_group, int limbs, bool accumulate,
+                          const Mod *mods, int logN, hipStream_t st);
 // out (+)= sum_i (K_i 2^sh_i mod q_l) * x_i   (x_i: [segs][limbs][n], common segment stride; sh may be null)
 void ew_linear_sum(u64 *out, const u64 *const *xs, const int64_t *K, int m, int limbs, int segs, size_t seg,
                    size_t xseg, const Mod *mods, int logN, hipStream_t st, bool accumulate = false,

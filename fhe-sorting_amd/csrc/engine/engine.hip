@@ -1656,6 +1656,62 @@ CtPtr Engine::mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Cipher
 }
 CtPtr Engine::square(const Ciphertext &a) { return mul(a, a); }
 
+// FHE_SORT_COLS_FUSED (A/B, default 1): mul_columns' tensor of every column in one pass
+static bool cols_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_SORT_COLS_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+
+CtPtr Engine::mul_columns(const Ciphertext &a, const std::vector<const Ciphertext *> &cols) {
+    auto &I = *impl;
+    if (cols.empty()) throw std::invalid_argument("mul_columns: no columns");
+    for (size_t p = 0; p < cols.size(); ++p) {
+        if (!cols[p]) throw std::invalid_argument("mul_columns: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1)
+            throw std::invalid_argument("mul_columns: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->level > a.level)
+            throw std::invalid_argument("mul_columns: column " + std::to_string(p) + " is at a higher level than a");
+    }
+    if (!cols_fused_enabled()) {
+        std::vector<CtPtr> prod;
+        std::vector<const Ciphertext *> v;
+        for (auto *c : cols) {
+            prod.push_back(mul(a, *c));
+            v.push_back(prod.back().get());
+        }
+        return prod.size() == 1 ? prod[0] : stack(v);
+    }
+    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    std::vector<CtPtr> adj;  // the columns mul would level-adjust, kept until the tensor pass is enqueued
+    std::vector<const u64 *> cp;
+    for (auto *c : cols) {
+        if (c->level < a.level) {
+            adj.push_back(level_adjust(*c, a.level));
+            c = adj.back().get();
+        }
+        if (c->limbs != a.limbs) throw std::invalid_argument("mul_columns: limb count mismatch");
+        cp.push_back(c->data);
+    }
+    const int B = a.batch, Pn = (int)cols.size(), PB = Pn * B;
+    ctr.hmult += PB;
+    ctr.keyswitch += PB;
+    ctr.rescale += PB;
+    const size_t nn = n(), ell = a.limbs;
+    count_bytes(6.0 * ell + ks_units(ell), PB);
+    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    dev::ew_tensor_cols(d01, d2, a.data, cp.data(), Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    const bool fuse = I.ks_fuse(PB);
+    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
+    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
+    return r;
+}
+
 std::vector<CtPtr> Engine::rotate_hoisted(const Ciphertext &a, const std::vector<long> &ks) {
     auto &I = *impl;
     std::vector<u64> gs;
@@ -2164,6 +2220,35 @@ CtPtr Engine::sum_members(const Ciphertext &a) {
     auto r = new_ct(a.level, a.slots, a.scale, a.limbs, 1);
     dev::ew_sum_members(r->data, a.data, a.batch, (int)a.limbs, MODS, LOGN, ST);
     return r;
+}
+void Engine::sum_member_groups(const Ciphertext &a, int groups, CtPtr &acc) {
+    if (groups < 1 || groups > 32767 || a.batch % groups)
+        throw std::invalid_argument("sum_member_groups: the batch is not a whole number of groups");
+    const int B = a.batch / groups;
+    if (acc && (acc->batch != groups || acc->level != a.level || acc->limbs != a.limbs))
+        throw std::invalid_argument("sum_member_groups: accumulator shape mismatch");
+    if (!cols_fused_enabled()) {  // the plain form (A/B): one sum_members per group, stacked
+        std::vector<CtPtr> sums;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < groups; ++p) {
+            Ciphertext g = a;
+            g.data = a.data + (size_t)p * B * 2 * a.limbs * n();
+            g.batch = B;
+            sums.push_back(sum_members(g));
+            v.push_back(sums.back().get());
+        }
+        CtPtr r = groups == 1 ? sums[0] : stack(v);
+        acc = acc ? add(*acc, *r) : r;
+        return;
+    }
+    const bool inplace = acc && acc.use_count() == 1 && acc->mem && acc->mem.use_count() == 1;
+    CtPtr r = inplace ? acc : new_ct(a.level, a.slots, a.scale, a.limbs, groups);
+    dev::ew_sum_member_groups(r->data, a.data, groups, B, (int)a.limbs, inplace, MODS, LOGN, ST);
+    count_bytes(2.0 * a.limbs * (B + 1) + (inplace ? 2.0 * a.limbs : 0.0), groups);
+    if (acc && !inplace)
+        acc = add(*acc, *r);
+    else
+        acc = r;
 }
 
 // =================================================== kernel-level (tests) ==

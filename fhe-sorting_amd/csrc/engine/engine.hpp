@@ -211,6 +211,14 @@ class Engine {
                   const std::vector<double> &cs, const Ciphertext *raw = nullptr, const Ciphertext *a_add = nullptr);
     // same with the sum already formed: raw = linear_sums_to(xs, {c}, level+1, false)[0]
     CtPtr mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add = nullptr);
+    // the stack a (B members) times each of P single ciphertexts: member p B + z
+    // of the result is mul(member(a, z), *cols[p]) word for word.  One tensor pass
+    // (k_tensor_cols), then mul's relinearisation / rescale tail on P B members.
+    // A column at a level lower than a's is level-adjusted to it as mul would; one
+    // at a higher level is refused (mul would adjust a instead, and the products
+    // would not share a level).  FHE_SORT_COLS_FUSED=0
+    // (A/B): P broadcast mul calls, stacked.
+    CtPtr mul_columns(const Ciphertext &a, const std::vector<const Ciphertext *> &cols);
     CtPtr square(const Ciphertext &a);
     CtPtr rotate(const Ciphertext &a, long k);
     std::vector<CtPtr> rotate_hoisted(const Ciphertext &a, const std::vector<long> &ks);
@@ -259,6 +267,11 @@ class Engine {
     CtPtr sub_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs);
     CtPtr sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps);
     CtPtr sum_members(const Ciphertext &a);
+    // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
+    // consecutive members, in one launch (k_sum_member_groups); an empty acc
+    // receives the sums, an exclusively owned one of the same level is added to
+    // in place.  FHE_SORT_COLS_FUSED=0 (A/B): one sum_members per group, stacked.
+    void sum_member_groups(const Ciphertext &a, int groups, CtPtr &acc);
     // sum over ranks already done into ct (u64 add, no reduction): reduce mod q
     void reduce_after_allreduce(Ciphertext &ct);
 

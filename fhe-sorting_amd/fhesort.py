@@ -19,6 +19,8 @@ PS_SPLIT_ENGINE, PS_SPLIT_OPENFHE = 0, 1  # fhe_set_ps_split (include/fhe_gpu.h)
 
 FHE_OK, FHE_EINVAL, FHE_ENOKEY, FHE_EDEPTH, FHE_EHIP, FHE_ENOMEM, FHE_EINTERNAL, FHE_ENOCOMM, FHE_EIO = range(9)
 NAF, BNAF, BINARY = 0, 1, 2
+SORT_COLUMN_MEMBERS_DEFAULT = 256  # fhe_set_sort_column_members' initial value (csrc/capi/capi.cpp)
+TENSOR_COLS_PER_THREAD = 4         # columns a k_tensor_cols thread owns (TC_PC, csrc/device/kernels.hip)
 
 
 class FheError(RuntimeError):
@@ -122,6 +124,11 @@ _SIGS = {
     'fhe_size_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
     'fhe_direct_sort': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, vp, vp, PP]),
+    'fhe_direct_sort_columns': (C.c_int, [vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, ip, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_void_p)]),
+    'fhe_set_sort_column_members': (C.c_int, [vp, C.c_int]),
+    'fhe_mul_columns': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_ct_sum_member_groups': (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -723,6 +730,41 @@ class Context:
                              cfg[0], cfg[1], cfg[2], mode, shard[0], shard[1], hk.ptr(), None)
         except FheError as e:
             hk.reraise(e)
+
+    def direct_sort_columns(self, key, cols, N, rots, cfg, rank=None, shard=(0, 1), allreduce=None):
+        """Records sorted by an encrypted key (fhe_direct_sort_columns): out[p] is
+        rotationIndexCheckN(rank(key), cols[p]) -- what direct_sort(cols[p], mode=2,
+        rank=...) gives, word for word -- with the index series evaluated once for
+        all columns.  rank=None: the rank is constructed from `key`; with a rank,
+        key may be None.  Pass the key among cols to get it sorted too.  With tied
+        keys the columns mix exactly as the key does (tests/tie_model.py)."""
+        r = np.asarray(rots, dtype=np.int32)
+        cols = list(cols)
+        arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
+        outs = (C.c_void_p * max(1, len(cols)))()
+        hk = _Hook(allreduce)
+        try:
+            _chk(lib().fhe_direct_sort_columns(self.h, None if key is None else key.h,
+                                               None if rank is None else rank.h, arr, len(cols), N, _int(r), len(r),
+                                               cfg[0], cfg[1], cfg[2], shard[0], shard[1], hk.ptr(), None, outs))
+        except FheError as e:
+            hk.reraise(e)
+        return [Ct(self, outs[i]) for i in range(len(cols))]
+
+    def mul_columns(self, a, cols):
+        """the stack a (B members) times each single ciphertext of cols: member
+        p * B + z of the result is mul(member(a, z), cols[p]) word for word"""
+        arr = (C.c_void_p * max(1, len(cols)))(*[c.h for c in cols])
+        return self._new(lib().fhe_mul_columns, a.h, arr, len(cols))
+
+    def sum_member_groups(self, a, groups):
+        """stack of `groups` members: member p = the sum of a's members p * B .. p * B + B - 1"""
+        return self._new(lib().fhe_ct_sum_member_groups, a.h, groups)
+
+    def set_sort_column_members(self, m):
+        """most members (columns x stacked batches) of one stacked column product
+        of direct_sort_columns; the words do not depend on it"""
+        _chk(lib().fhe_set_sort_column_members(self.h, m))
 
     def sort_hybrid(self, x, N, rots, cfg, mode=0, rank=None, max_array=256, mask=0, shard=(0, 1), allreduce=None):
         """DirectSort::sort_hybrid (mode 0) or rotationIndexCheckHybrid(rank, x) (mode 1)."""

@@ -238,6 +238,35 @@ int fhe_direct_sort(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
                     int n, int dg, int df, int mode, int shard_rank, int shard_world, fhe_allreduce_fn allreduce,
                     void *user, fhe_ct **out);
 
+/* Records sorted by an encrypted key.  out[p] = rotationIndexCheckN(rank(key), cols[p]),
+ * word for word what ncols calls of fhe_direct_sort(mode 2) give, with the index
+ * series evaluated once.  rank == NULL: constructRank(key) first (key must then be
+ * given); rank != NULL: key may be NULL (apply a known rank to the columns).
+ * Pass the key among cols to get it sorted too.  Sharding as fhe_direct_sort.
+ * FHE_EINVAL (the message names the column) for ncols < 1, a null column, a column
+ * that is a stack, a column whose slot count differs from the rank's (or, without a
+ * rank, the key's), and for a missing key and rank; FHE_EDEPTH for a column below
+ * the level of the series output (the product could not meet it there), raised
+ * before the index check starts.  On failure no output handle is set.  With tied
+ * keys the columns are mixed exactly as the key is (tests/tie_model.py): a true
+ * permutation needs distinct keys. */
+int fhe_direct_sort_columns(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols,
+                            int ncols, int N, const int32_t *rots, int nrot, int n, int dg, int df,
+                            int shard_rank, int shard_world, fhe_allreduce_fn allreduce, void *user,
+                            fhe_ct **outs /* ncols handles */);
+/* most members (columns x stacked batches) of one stacked column product of
+ * fhe_direct_sort_columns (default 256, or FHE_SORT_COLS_MEMBERS at context
+ * creation; HBM use grows with it); more columns run in groups.  Results do
+ * not depend on it. */
+int fhe_set_sort_column_members(fhe_ctx *ctx, int max_members);
+/* for tests and bindings, like fhe_mul_add: the stack a (B members) times ncols
+ * single ciphertexts, member p B + z = fhe_mul_relin(member z, cols[p]) word for
+ * word (one tensor pass; FHE_SORT_COLS_FUSED=0: ncols broadcast products,
+ * stacked); and out[p] = sum_z a[p B + z] for `groups` groups of consecutive
+ * members in one launch (under the same switch: one member sum per group) */
+int fhe_mul_columns(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *cols, int ncols, fhe_ct **out_stack);
+int fhe_ct_sum_member_groups(fhe_ctx *ctx, const fhe_ct *a, int groups, fhe_ct **out_stack);
+
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
  * grows with it).  Results do not depend on it. */
