@@ -246,9 +246,8 @@ struct PSEval {
         if (r.size() == 1 && r[0] == 0.0) return cc.mul(*qv, giant(G));
         if (folded(r)) {
             CtPtr rawsum = leaf();  // the collected raw leaf (same order as collect)
-            CtPtr out = cc.mul_add_raw(*qv, giant(G), *rawsum);
-            if (r[0] != 0.0) cc.add_const_inplace(out, r[0]);
-            return out;
+            // + r_0 inside the product (Engine::mul_add's out_const)
+            return cc.mul_add_raw(*qv, giant(G), *rawsum, nullptr, 0.0, r[0]);
         }
         CtPtr prod = cc.mul(*qv, giant(G));
         CtPtr rv = eval(r, target);
@@ -524,32 +523,32 @@ struct PSOpenFHE {
     // single rescale (OpenFHE doubles before its deferred rescale as well); an
     // operand below the other's level is doubled by the level-adjusting
     // constant product itself
-    CtPtr twice_prod(const Ciphertext &a, const Ciphertext &b, const Ciphertext *x, double cx) {
+    // c0 (0 = none): a constant added to the product inside its tensor pass
+    // (Engine::mul_add's out_const: add_const_inplace's words)
+    CtPtr twice_prod(const Ciphertext &a, const Ciphertext &b, const Ciphertext *x, double cx, double c0 = 0.0) {
         const Ciphertext *lo = &a, *hi = &b;
         if (lo->level > hi->level) std::swap(lo, hi);
         // equal levels: (lo + lo) hi with the sum formed on load in the tensor pass
         // (a square doubles its left operand only)
         if (lo->level == hi->level && fold_scalars())
             return cc.mul_add(*lo, *hi, x ? std::vector<const Ciphertext *>{x} : std::vector<const Ciphertext *>{},
-                              x ? std::vector<double>{cx} : std::vector<double>{}, nullptr, lo);
+                              x ? std::vector<double>{cx} : std::vector<double>{}, nullptr, lo, 0.0, c0);
         CtPtr a2 =lo->level < hi->level ? cc.mul_const_to(*lo, 2.0, hi->level) : cc.add(*lo, *lo);
-        if (!x) return cc.mul(*a2, *hi);
-        return cc.mul_add(*a2, *hi, {x}, {cx});
+        if (!x) return cc.mul_add(*a2, *hi, {}, {}, nullptr, nullptr, 0.0, c0);
+        return cc.mul_add(*a2, *hi, {x}, {cx}, nullptr, nullptr, 0.0, c0);
     }
     // T_i: powers of two and even i by 2 T_{i/2}^2 - 1, odd i by 2 T_{i/2} T_{i/2+1} - T_1
     void build() {
         for (int i = 2; i <= k; ++i) {
             if (i % 2 == 0) {
-                T[i] = twice_prod(*T[i / 2], *T[i / 2], nullptr, 0.0);
-                cc.add_const_inplace(T[i], -1.0);
+                T[i] = twice_prod(*T[i / 2], *T[i / 2], nullptr, 0.0, -1.0);
             } else {
                 T[i] = twice_prod(*T[i / 2], *T[i / 2 + 1], T[1].get(), -1.0);
             }
         }
         T2.push_back(T[k]);
         for (int j = 1; j < m; ++j) {
-            T2.push_back(twice_prod(*T2[j - 1], *T2[j - 1], nullptr, 0.0));
-            cc.add_const_inplace(T2.back(), -1.0);
+            T2.push_back(twice_prod(*T2[j - 1], *T2[j - 1], nullptr, 0.0, -1.0));
         }
     }
     // T_{k(2^m - 1)} = 2 T_{k(2^(j) - 1)} T_{k 2^j} - T_k, j = 1..m-1
@@ -600,19 +599,20 @@ struct PSOpenFHE {
     // node at depth mm: (T2[mm-1] + c) q + s, output level lk + mm
     CtPtr node(const OFNode &N) {
         // a = T2[mm-1] + c(u): with c(u) a leaf the sum is formed inside the
-        // product's tensor pass (Engine::mul_add's a_add; same words)
+        // product's tensor pass (Engine::mul_add's a_add; same words); without
+        // one the constant c0 is added there on load (a_const), and a leaf
+        // remainder's constant s0 as a term of d0 (out_const)
         CtPtr cu = N.cu >= 0 ? leaf(N.cu) : nullptr;
-        CtPtr a = cu ? T2[N.mm - 1] : (N.c0 != 0.0 ? cc.add_const(*T2[N.mm - 1], N.c0) : T2[N.mm - 1]);
+        const CtPtr &a = T2[N.mm - 1];
+        const double c0 = cu ? 0.0 : N.c0;
         CtPtr qu = N.qn ? node(*N.qn) : leaf(N.qleaf);
         if (N.sn) {
             CtPtr su = node(*N.sn);  // level lk + mm - 1: added before the product's rescale
-            return cc.mul_add(*a, *qu, {su.get()}, {1.0}, nullptr, cu.get());
+            return cc.mul_add(*a, *qu, {su.get()}, {1.0}, nullptr, cu.get(), c0);
         }
         const double s0 = P->leaves[N.sleaf].a[0];
         CtPtr raw = leaf(N.sleaf);
-        CtPtr out = cc.mul_add_raw(*a, *qu, *raw, cu.get());
-        if (s0 != 0.0) cc.add_const_inplace(out, s0);
-        return out;
+        return cc.mul_add_raw(*a, *qu, *raw, cu.get(), c0, s0);
     }
     CtPtr run() {
         build();
@@ -1358,22 +1358,19 @@ std::vector<CtPtr> DirectSortN::vecRotsOptMany(Lane L, const std::vector<CtPtr> 
                                                int num_slots, int np, const std::vector<int> &iss) {
     if (iss.size() == 1) return {vecRotsOpt(L, baby, num_partition, num_slots, np, iss[0])};
     std::vector<CtPtr> result(iss.size());
+    // the baby steps are the same for every batch, only the masks differ: one
+    // pass forms the chunk's masked sums as the stack rotateMembers takes
+    std::vector<const Ciphertext *> cs;
+    for (int i = 0; i < np; ++i) cs.push_back(baby[i].get());
     for (int j = 0; j < num_partition / np; ++j) {
-        std::vector<CtPtr> T(iss.size());
-        std::vector<const Ciphertext *> tp;
+        std::vector<std::vector<const Plaintext *>> ps(iss.size());
         std::vector<int> rots;
         for (size_t b = 0; b < iss.size(); ++b) {
-            std::vector<const Ciphertext *> cs;
-            std::vector<const Plaintext *> ps;
-            for (int i = 0; i < np; ++i) {
-                cs.push_back(baby[i].get());
-                ps.push_back(&mask(*L.eng, 0, num_slots, np * j + i, -iss[b] * num_partition - j * np, baby[i]->level));
-            }
-            T[b] = L.eng->mul_plain_sum(cs, ps);
-            tp.push_back(T[b].get());
+            for (int i = 0; i < np; ++i)
+                ps[b].push_back(&mask(*L.eng, 0, num_slots, np * j + i, -iss[b] * num_partition - j * np, baby[i]->level));
             rots.push_back(iss[b] * num_partition + j * np);
         }
-        auto o = L.rot->rotateMembers(*L.eng->stack(tp), rots);
+        auto o = L.rot->rotateMembers(*L.eng->mul_plain_sum_batches(cs, ps), rots);
         for (size_t b = 0; b < iss.size(); ++b) L.eng->add_inplace(result[b], *o[b]);
     }
     return result;

@@ -260,6 +260,29 @@ int fhe_mul_plain_sum(fhe_ctx *ctx, const fhe_ct *const *cts, const fhe_pt *cons
         *out = wrap(ctx->eng->mul_plain_sum(a, p));
     });
 }
+int fhe_mul_plain_sum_batches(fhe_ctx *ctx, const fhe_ct *const *cts, const fhe_pt *const *pts, int m, int nb,
+                              fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        if (m < 1 || nb < 1) throw std::invalid_argument("fhe_mul_plain_sum_batches: m and nb must be positive");
+        std::vector<const Ciphertext *> a;
+        std::vector<std::vector<const Plaintext *>> p(nb);
+        for (int i = 0; i < m; ++i) {
+            NEED(cts[i]);
+            a.push_back(cts[i]->p.get());
+        }
+        for (int b = 0; b < nb; ++b)
+            for (int i = 0; i < m; ++i) {
+                NEED(pts[(size_t)b * m + i]);
+                p[b].push_back(pts[(size_t)b * m + i]->p.get());
+            }
+        *out = wrap(ctx->eng->mul_plain_sum_batches(a, p));
+    });
+}
+int fhe_plain_sum_tile(void) { return fhe::dev::plain_sum_tile(); }
+double fhe_plain_sum_batches_limb_units(int m, int nb, int tile) {
+    return tile > 0 ? fhe::dev::plain_sum_batches_limb_units(m, nb, tile) : -1.0;
+}
 int fhe_ct_stack(fhe_ctx *ctx, const fhe_ct *const *xs, int m, fhe_ct **out) {
     return guard([&] {
         NEED(ctx);
@@ -350,6 +373,24 @@ int fhe_mul_add(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *co
         *out = wrap(ctx->eng->mul_add(*a->p, *b->p, v, std::vector<double>(c, c + m), raw ? raw->p.get() : nullptr,
                                       a_add ? a_add->p.get() : nullptr));
     });
+}
+int fhe_mul_add_const(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *const *xs, const double *c, int m,
+                      const fhe_ct *raw, const fhe_ct *a_add, double a_const, double out_const, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(b);
+        std::vector<const Ciphertext *> v;
+        for (int i = 0; i < m; ++i) {
+            NEED(xs[i]);
+            v.push_back(xs[i]->p.get());
+        }
+        *out = wrap(ctx->eng->mul_add(*a->p, *b->p, v, std::vector<double>(c, c + m), raw ? raw->p.get() : nullptr,
+                                      a_add ? a_add->p.get() : nullptr, a_const, out_const));
+    });
+}
+int fhe_mul_fold_left(int enabled, int a_level, int b_level) {
+    return Engine::mul_fold_left(enabled != 0, a_level, b_level) ? 1 : 0;
 }
 int fhe_add_const(fhe_ctx *ctx, const fhe_ct *a, double c, fhe_ct **out) {
     return guard([&] { *out = wrap(ctx->eng->add_const(*a->p, c)); });

@@ -285,6 +285,116 @@ __global__ __launch_bounds__(NT) void k_tensor_lin(u64 *d01, u64 *d2, const u64 
     }
     st2(d2 + z * ln_all + o, e2);
 }
+// k_tensor / k_tensor_lin<M> with constants (Engine::mul_add's a_const, out_const).
+// They are kernels of their own, so the plain forms above keep their code and registers.
+// C.aK (0 = none): the constant aK 2^ash is added to the left operand's c0 after
+// a2 (the PS node's T_{k 2^j} + c0: add_const's words without its pass).
+// C.oK (0 = none): the constant oK 2^osh, at the product's scale after its
+// rescale, joins d0 as (oK 2^osh) q_last mod q_l on the limbs below the last:
+// the HMult tail is linear in d0 and divides by q_last, the last limb (the one
+// the rescale lifts) is unchanged, so the canonical words it stores are those of
+// add_const on the rescaled product.  The limb's residues are formed once per block.
+struct TensorConst {
+    int64_t aK = 0, oK = 0;
+    int ash = 0, osh = 0;
+};
+// (K 2^sh) q_last mod q_l, zero on the last limb (gridDim.y limbs)
+__device__ __forceinline__ u64 tensor_out_const(int64_t K, int sh, const Mod &m, const Mod *mods, int l) {
+    const int last = (int)gridDim.y - 1;
+    return l == last ? 0 : mul_barrett(smod(K, sh, m), reduce64(mods[last].q, m), m);
+}
+__global__ __launch_bounds__(NT) void k_tensor_c(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
+                                                 size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorConst C,
+                                                 const Mod *mods, int logN) {
+    __shared__ u64 wc[2];
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const Mod m = mods[l];
+    if (threadIdx.x == 0) wc[0] = smod(C.aK, C.ash, m);
+    if (threadIdx.x == 1) wc[1] = C.oK ? tensor_out_const(C.oK, C.osh, m, mods, l) : 0;
+    __syncthreads();
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const size_t z = blockIdx.z, o = (size_t)l * n + k;
+    const u64 *A = a + z * sa, *Bp = b + z * sb;
+    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
+    if (a2) {
+        const u64 *A2 = a2 + z * sa2;
+        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
+        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
+        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
+    }
+    const u64 wa = wc[0], wo = wc[1];
+    a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
+    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
+    ulonglong2 e0, e1, e2;
+    e0.x = add_mod(mul_barrett(a0.x, b0.x, m), wo, m.q);
+    e0.y = add_mod(mul_barrett(a0.y, b0.y, m), wo, m.q);
+    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
+    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
+    e2.x = mul_barrett(a1.x, b1.x, m);
+    e2.y = mul_barrett(a1.y, b1.y, m);
+    st2(d01 + z * 2 * ln_all + o, e0);
+    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
+    st2(d2 + z * ln_all + o, e2);
+}
+template <int M>
+__global__ __launch_bounds__(NT) void k_tensor_lin_c(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
+                                                     size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorConst C,
+                                                     TensorLin L, const Mod *mods, int logN) {
+    __shared__ u64 w[TL_MAX + 2];  // the summands' constants, then the left operand's and d0's
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const Mod m = mods[l];
+    if ((int)threadIdx.x < M) w[threadIdx.x] = smod(L.K[threadIdx.x], L.sh[threadIdx.x], m);
+    if (threadIdx.x == TL_MAX) w[TL_MAX] = smod(C.aK, C.ash, m);
+    if (threadIdx.x == TL_MAX + 1) w[TL_MAX + 1] = C.oK ? tensor_out_const(C.oK, C.osh, m, mods, l) : 0;
+    __syncthreads();
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const size_t z = blockIdx.z, o = (size_t)l * n + k;
+    const u64 *A = a + z * sa, *Bp = b + z * sb;
+    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
+    if (a2) {
+        const u64 *A2 = a2 + z * sa2;
+        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
+        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
+        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
+    }
+    {
+        const u64 wa = w[TL_MAX];
+        a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
+    }
+    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
+    ulonglong2 xs[2][M];  // the summands' loads issued with the operands'
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int i = 0; i < M; ++i) xs[p][i] = ld2(L.x[i] + (2 * z + p) * L.xseg + o);
+    Acc128 r[2][2];
+    r[0][0].lo = mul_barrett(a0.x, b0.x, m);
+    r[0][1].lo = mul_barrett(a0.y, b0.y, m);
+    r[1][0].lo = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
+    r[1][1].lo = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
+    ulonglong2 e2;
+    e2.x = mul_barrett(a1.x, b1.x, m);
+    e2.y = mul_barrett(a1.y, b1.y, m);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            mac128(r[p][0], xs[p][i].x, w[i]);
+            mac128(r[p][1], xs[p][i].y, w[i]);
+        }
+        ulonglong2 v = make_ulonglong2(reduce128(r[p][0], m), reduce128(r[p][1], m));
+        if (p == 0) {  // read here, so it is not live across the sums
+            const u64 wo = w[TL_MAX + 1];
+            v = make_ulonglong2(add_mod(v.x, wo, m.q), add_mod(v.y, wo, m.q));
+        }
+        st2(d01 + z * 2 * ln_all + p * ln_all + o, v);
+    }
+    st2(d2 + z * ln_all + o, e2);
+}
 // out [2][limbs][n] = sum over members of in [members][2][limbs][n]
 __global__ __launch_bounds__(NT) void k_sum_members(u64 *out, const u64 *in, int members, size_t ln_all,
                                                     const Mod *mods, int logN) {
@@ -1083,6 +1193,90 @@ __global__ __launch_bounds__(NT) void k_mul_plain_sum(u64 *out, PlainSumArgs A, 
         mac128(r1, x.y, p.y);
     }
     st2(o, make_ulonglong2(reduce128(r0, md), reduce128(r1, md)));
+}
+
+// k_mul_plain_sum for nb batches over one list of single ciphertexts:
+// out[2 b + c] = sum_i ct_i[c] * pt[b][i]  (accumulate: + out), b < nb.  The
+// ciphertexts are the same for every batch (constructRank's baby steps), only the
+// masks differ, so a thread keeps the 2 x 2 sums of PSB_TB batches (16 lazy
+// 128-bit accumulators, 64 VGPRs), loads each ct_i pair once per tile and
+// applies it to the tile's masks: 2 m ceil(nb / TB) + m nb + 2 nb limb-units
+// against nb (3 m + 2).  The sums are exact, so the words are k_mul_plain_sum's.
+// pt: device table [nb][mtot], this launch's terms at column `base`.  A last
+// tile narrower than PSB_TB repeats its last batch and stores only the valid ones.
+// grid: as k_mul_plain_sum with the batch tile in the segment's place -- flat
+// and XCD-grouped (A.xcd), so the tiles that read one ciphertext block run on
+// one XCD and share it in that L2; else x = batch tile, y = coefficient block,
+// z = limb.
+constexpr int PSB_TB = 4;
+struct PlainSumBatchArgs {
+    const u64 *ct[LIN_MAX];
+    const u64 *const *pt;
+    int m, base, mtot, nb, accumulate;
+    size_t cpoly;
+    int xcd, btiles, cblocks;
+};
+__global__ __launch_bounds__(NT) void k_mul_plain_sum_batches(u64 *out, PlainSumBatchArgs A, size_t seg,
+                                                              const Mod *mods, int logN) {
+    constexpr int TB = PSB_TB;
+    const size_t n = (size_t)1 << logN;
+    int l, bt, cb;
+    if (A.xcd) {
+        const unsigned b = blockIdx.x, j = b >> 3;
+        const unsigned tile = 8 * (j / (unsigned)A.btiles) + (b & 7);
+        bt = (int)(j % (unsigned)A.btiles);
+        cb = (int)(tile % (unsigned)A.cblocks);
+        l = (int)(tile / (unsigned)A.cblocks);
+    } else {
+        l = blockIdx.z;
+        bt = blockIdx.x;
+        cb = blockIdx.y;
+    }
+    const size_t k = ((size_t)cb * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod md = mods[l];
+    // every operand is a block-uniform base plus this lane's byte offset, which fits
+    // 32 bits (checked at launch): one offset register serves every load and store
+    const unsigned off = (unsigned)(((size_t)l * n + k) * 8);
+    auto at = [off](const u64 *base) { return reinterpret_cast<const u64 *>(reinterpret_cast<const char *>(base) + off); };
+    const int b0 = bt * TB;
+    const u64 *const *prow[TB];  // the masks of the tile's batches (block-uniform)
+#pragma unroll
+    for (int t = 0; t < TB; ++t) prow[t] = A.pt + (size_t)min(b0 + t, A.nb - 1) * A.mtot + A.base;
+    Acc128 r[TB][2][2];
+    if (A.accumulate) {
+#pragma unroll
+        for (int t = 0; t < TB; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const ulonglong2 v = ld2(at(out + (size_t)(2 * min(b0 + t, A.nb - 1) + c) * seg));
+                r[t][c][0].lo = v.x;
+                r[t][c][1].lo = v.y;
+            }
+    }
+#pragma unroll 1
+    for (int i = 0; i < A.m; ++i) {
+        const u64 *c = A.ct[i];
+        const ulonglong2 x0 = ld2(at(c)), x1 = ld2(at(c + A.cpoly));
+        ulonglong2 p[TB];
+#pragma unroll
+        for (int t = 0; t < TB; ++t) p[t] = ld2(at(prow[t][i]));
+#pragma unroll
+        for (int t = 0; t < TB; ++t) {
+            mac128(r[t][0][0], x0.x, p[t].x);
+            mac128(r[t][0][1], x0.y, p[t].y);
+            mac128(r[t][1][0], x1.x, p[t].x);
+            mac128(r[t][1][1], x1.y, p[t].y);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < TB; ++t)
+        if (b0 + t < A.nb) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                st2(const_cast<u64 *>(at(out + (size_t)(2 * (b0 + t) + c) * seg)),
+                    make_ulonglong2(reduce128(r[t][c][0], md), reduce128(r[t][c][1], md)));
+        }
 }
 
 // grid: x = n / NT, y = limb, z = segment
@@ -2601,13 +2795,17 @@ void ew_add_scaled(u64 *out, const u64 *a, const LimbConsts &W, int limbs, Seg S
 void ew_add_scalar(u64 *out, const u64 *a, int64_t K, int limbs, int segs, Seg S, const Mod *mods, int logN,
                    hipStream_t st, int sh) {
     if (limbs <= 0 || segs <= 0) return;
-    hipLaunchKernelGGL(k_add_scalar, ew_grid(logN, limbs, segs), dim3(NT), 0, st, out, a, K, sh, S, mods, logN);
+    const double B = 8.0 * 2 * limbs * segs * ((size_t)1 << logN);
+    launch_clocked("k_add_scalar", B, k_add_scalar, ew_grid(logN, limbs, segs), dim3(NT), st, out, a, K, sh, S, mods,
+                   logN);
 }
 void ew_c0_op(u64 *out, const u64 *a, const u64 *p, int64_t K, int sh, int mode, int limbs, int members,
               const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0) return;
-    hipLaunchKernelGGL(k_c0_op, ew_grid(logN, limbs, 2 * members), dim3(NT), 0, st, out, a, p, K, sh, mode,
-                       (size_t)limbs << logN, mods, logN);
+    // both polynomials read and written, the plaintext (modes 1-3) read once per member
+    const double B = 8.0 * (4.0 + (p ? 1.0 : 0.0)) * limbs * members * ((size_t)1 << logN);
+    launch_clocked("k_c0_op", B, k_c0_op, ew_grid(logN, limbs, 2 * members), dim3(NT), st, out, a, p, K, sh, mode,
+                   (size_t)limbs << logN, mods, logN);
 }
 void ew_mul_plain(u64 *out, const u64 *a, const u64 *p, int limbs, int segs, Seg S, const Mod *mods, int logN,
                   hipStream_t st) {
@@ -2615,16 +2813,21 @@ void ew_mul_plain(u64 *out, const u64 *a, const u64 *p, int limbs, int segs, Seg
     hipLaunchKernelGGL(k_mul_plain, ew_grid(logN, limbs, segs), dim3(NT), 0, st, out, a, p, S, mods, logN);
 }
 void ew_tensor(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int members, size_t sa, size_t sb,
-               const Mod *mods, int logN, hipStream_t st, const u64 *a2, size_t sa2) {
+               const Mod *mods, int logN, hipStream_t st, const u64 *a2, size_t sa2, int64_t aK, int ash, int64_t oK,
+               int osh) {
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
     const double B = 8.0 * (5.0 * members + 2.0 * (sb ? members : 1) + (a2 ? 2.0 * members : 0.0)) * ln_all;
-    launch_clocked("k_tensor", B, k_tensor, ew_grid(logN, limbs, members), dim3(NT), st, d01, d2, a, b, ln_all, sa, sb,
-                   a2, sa2, mods, logN);
+    if (aK || oK)
+        launch_clocked("k_tensor_c", B, k_tensor_c, ew_grid(logN, limbs, members), dim3(NT), st, d01, d2, a, b, ln_all,
+                       sa, sb, a2, sa2, TensorConst{aK, oK, ash, osh}, mods, logN);
+    else
+        launch_clocked("k_tensor", B, k_tensor, ew_grid(logN, limbs, members), dim3(NT), st, d01, d2, a, b, ln_all, sa,
+                       sb, a2, sa2, mods, logN);
 }
 bool ew_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int members, size_t sa, size_t sb,
                    const u64 *const *xs, const int64_t *K, const uint8_t *sh, int m, size_t xseg, const Mod *mods,
-                   int logN, hipStream_t st, const u64 *a2, size_t sa2) {
+                   int logN, hipStream_t st, const u64 *a2, size_t sa2, int64_t aK, int ash, int64_t oK, int osh) {
     if (m < 1 || m > TL_MAX || limbs <= 0 || members <= 0) return false;
     const size_t ln_all = (size_t)limbs << logN;
     TensorLin L{};
@@ -2638,8 +2841,13 @@ bool ew_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int
                      ln_all;
     dispatch_int<1, TL_MAX>(m, [&](auto mm) {
         constexpr int MM = decltype(mm)::value;
-        launch_clocked(inst_name<MM>("k_tensor_lin"), B, k_tensor_lin<MM>, ew_grid(logN, limbs, members), dim3(NT), st,
-                       d01, d2, a, b, ln_all, sa, sb, a2, sa2, L, mods, logN);
+        if (aK || oK)
+            launch_clocked(inst_name<MM>("k_tensor_lin_c"), B, k_tensor_lin_c<MM>, ew_grid(logN, limbs, members),
+                           dim3(NT), st, d01, d2, a, b, ln_all, sa, sb, a2, sa2, TensorConst{aK, oK, ash, osh}, L, mods,
+                           logN);
+        else
+            launch_clocked(inst_name<MM>("k_tensor_lin"), B, k_tensor_lin<MM>, ew_grid(logN, limbs, members), dim3(NT),
+                           st, d01, d2, a, b, ln_all, sa, sb, a2, sa2, L, mods, logN);
     });
     return true;
 }
@@ -2818,6 +3026,46 @@ void ew_mul_plain_sum(u64 *out, const u64 *const *cts, const u64 *const *pts, in
         } else {
             launch_clocked("k_mul_plain_sum", B, k_mul_plain_sum, dim3(g0.z, g0.x, g0.y), dim3(NT), st, out, A, seg,
                            mods, logN);
+        }
+    }
+}
+int plain_sum_tile() { return PSB_TB; }
+double plain_sum_batches_limb_units(int m, int nb, int tile) {
+    return 2.0 * m * ((nb + tile - 1) / tile) + (double)m * nb + 2.0 * nb;
+}
+void ew_mul_plain_sum_batches(u64 *out, const u64 *const *cts, const u64 *const *pts, int m, int nb, int limbs,
+                              size_t cpoly, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || nb <= 0 || m <= 0) return;
+    const size_t seg = (size_t)limbs << logN;
+    if (seg * 8 >= (1ull << 32)) throw std::invalid_argument("ew_mul_plain_sum_batches: polynomial beyond 32-bit offsets");
+    const int btiles = (nb + PSB_TB - 1) / PSB_TB;
+    for (int base = 0; base < m; base += LIN_MAX) {
+        PlainSumBatchArgs A{};
+        A.m = std::min(LIN_MAX, m - base);
+        A.base = base;
+        A.mtot = m;
+        A.nb = nb;
+        A.accumulate = base > 0;
+        A.cpoly = cpoly;
+        A.pt = pts;
+        A.btiles = btiles;
+        for (int i = 0; i < A.m; ++i) A.ct[i] = cts[base + i];
+        const double B = 8.0 * (plain_sum_batches_limb_units(A.m, nb, PSB_TB) + 2.0 * nb * A.accumulate) * limbs *
+                         ((size_t)1 << logN);
+        const dim3 g0 = ew_grid(logN, limbs, btiles);
+        static const int xcd_env = [] {  // FHE_PS_XCD, as ew_mul_plain_sum
+            const char *e = std::getenv("FHE_PS_XCD");
+            return e ? std::atoi(e) : 1;
+        }();
+        const unsigned tiles = g0.x * g0.y;
+        if (xcd_env && tiles % 8 == 0 && (size_t)tiles * g0.z < (1ull << 31)) {
+            A.xcd = 1;
+            A.cblocks = (int)g0.x;
+            launch_clocked("k_mul_plain_sum_batches", B, k_mul_plain_sum_batches, dim3(tiles * g0.z), dim3(NT), st, out,
+                           A, seg, mods, logN);
+        } else {
+            launch_clocked("k_mul_plain_sum_batches", B, k_mul_plain_sum_batches, dim3(g0.z, g0.x, g0.y), dim3(NT), st,
+                           out, A, seg, mods, logN);
         }
     }
 }

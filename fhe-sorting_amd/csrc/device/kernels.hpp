@@ -195,13 +195,18 @@ void ew_mul_plain(u64 *out, const u64 *a, const u64 *p, int limbs, int segs, Seg
 // per member m: d0 = a0 b0, d1 = a0 b1 + a1 b0 -> d01 [m][2][limbs][n]; d2 = a1 b1 -> d2 [m][limbs][n]
 // (a member m at m * sa, b member at m * sb; sb = 0 broadcasts one ciphertext)
 void ew_tensor(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int members, size_t sa, size_t sb,
-               const Mod *mods, int logN, hipStream_t st, const u64 *a2 = nullptr, size_t sa2 = 0);
+               const Mod *mods, int logN, hipStream_t st, const u64 *a2 = nullptr, size_t sa2 = 0, int64_t aK = 0,
+               int ash = 0, int64_t oK = 0, int osh = 0);
+// (aK 2^ash: a constant added to the left operand's c0 on load, after a2; oK 2^osh: a
+// constant the rescaled product's c0 takes, added to d0 as (oK 2^osh) q_last below the
+// last limb -- the words of add_const after the HMult tail; 0 = none)
 // ew_tensor with d_p += sum_i (K_i 2^sh_i mod q) x_i[2 member + p] (x_i segment
 // stride xseg) for 1 <= m <= 4 summands; false (nothing launched) otherwise.
 // Word-identical to ew_tensor then ew_linear_sum(d01, ..., accumulate).
 bool ew_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int members, size_t sa, size_t sb,
                    const u64 *const *xs, const int64_t *K, const uint8_t *sh, int m, size_t xseg, const Mod *mods,
-                   int logN, hipStream_t st, const u64 *a2 = nullptr, size_t sa2 = 0);
+                   int logN, hipStream_t st, const u64 *a2 = nullptr, size_t sa2 = 0, int64_t aK = 0, int ash = 0,
+                   int64_t oK = 0, int osh = 0);
 // out [2][limbs][n] = sum_m in [m][2][limbs][n]
 void ew_sum_members(u64 *out, const u64 *in, int members, int limbs, const Mod *mods, int logN, hipStream_t st);
 // ew_tensor of a's `members` members (stride sa) against each of P single
@@ -235,6 +240,16 @@ bool linear_sums_on_mfma(int logN);
 // c1 at + cpoly; pt_i [limbs][n] shared), lazy 128-bit accumulation
 void ew_mul_plain_sum(u64 *out, const u64 *const *cts, const u64 *const *pts, int m, int limbs, int members,
                       size_t cmember, size_t cpoly, const Mod *mods, int logN, hipStream_t st);
+// The masked sums of nb batches over one list of m single ciphertexts
+// (cts[i]: [2][limbs][n], c1 at + cpoly): out[2 b + c] = sum_i cts[i][c] * pts[b * m + i],
+// segment stride limbs n.  A thread holds the sums of up to plain_sum_tile()
+// batches and loads each ciphertext pair once for all of them; word for word
+// nb ew_mul_plain_sum calls.
+int plain_sum_tile();
+// the bytes one such pass moves, in limbs of n words (the launches' clocked bytes)
+double plain_sum_batches_limb_units(int m, int nb, int tile);
+void ew_mul_plain_sum_batches(u64 *out, const u64 *const *cts, const u64 *const *pts, int m, int nb, int limbs,
+                              size_t cpoly, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);

@@ -255,6 +255,36 @@ struct Engine::Impl {
         return {reinterpret_cast<const int64_t *>(b), reinterpret_cast<const uint8_t *>(b + K.size() * sizeof(int64_t))};
     }
 
+    // device copies of mul_plain_sum_batches' plaintext pointer tables ([nb][m]),
+    // keyed by their bytes like the constant tables: the rank's masks are cached
+    // plaintexts, so a sort after the first finds its table and uploads nothing
+    struct PtrTab {
+        std::shared_ptr<DevMem> mem;
+        std::vector<const u64 *> host;  // stays alive for the asynchronous upload
+        u64 used = 0;
+    };
+    std::map<std::string, PtrTab> ptabs;
+    const u64 *const *ptr_table(const std::vector<const u64 *> &v) {
+        std::string key(reinterpret_cast<const char *>(v.data()), v.size() * sizeof(const u64 *));
+        auto it = ptabs.find(key);
+        if (it == ptabs.end()) {
+            if (ptabs.size() >= 256) {
+                auto lru = ptabs.begin();
+                for (auto j = ptabs.begin(); j != ptabs.end(); ++j)
+                    if (j->second.used < lru->second.used) lru = j;
+                HIP_OK(hipStreamSynchronize(st));
+                ptabs.erase(lru);
+            }
+            PtrTab t;
+            t.host = v;
+            t.mem = alloc(v.size() * sizeof(const u64 *));
+            HIP_OK(hipMemcpyAsync(t.mem->p, t.host.data(), v.size() * sizeof(const u64 *), hipMemcpyHostToDevice, st));
+            it = ptabs.emplace(std::move(key), std::move(t)).first;
+        }
+        it->second.used = ++ctab_tick;
+        return static_cast<const u64 *const *>(it->second.mem->p);
+    }
+
     // device encoder tables (the host encoder's ksi / rot, uploaded on first use)
     const double2 *enc_ksi = nullptr;
     const uint32_t *enc_rot = nullptr;
@@ -1550,6 +1580,62 @@ CtPtr Engine::mul_plain_sum(const std::vector<const Ciphertext *> &a, const std:
     return r;
 }
 
+// FHE_RANK_STACK_MASKS (A/B, default 1): the masked sums of a chunk's batches in
+// one pass over the shared ciphertexts; 0: one mul_plain_sum per batch, stacked
+static bool stack_masks_enabled() {
+    static const bool on = [] {
+        const char *e = std::getenv("FHE_RANK_STACK_MASKS");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return on;
+}
+
+// member b = sum_i a_i * p[b][i] with one rescale: nb mul_plain_sum calls over
+// the same single ciphertexts, word for word, with their counters and op bytes
+CtPtr Engine::mul_plain_sum_batches(const std::vector<const Ciphertext *> &a,
+                                    const std::vector<std::vector<const Plaintext *>> &p) {
+    auto &I = *impl;
+    if (a.empty() || p.empty()) throw std::invalid_argument("mul_plain_sum_batches: bad operand lists");
+    const int level = a[0]->level, nb = (int)p.size();
+    const size_t m = a.size();
+    for (size_t i = 0; i < m; ++i) {
+        if (a[i]->level != level) throw std::invalid_argument("mul_plain_sum_batches: level mismatch");
+        if (a[i]->batch != 1) throw std::invalid_argument("mul_plain_sum_batches: single ciphertexts only");
+    }
+    for (auto &row : p) {
+        if (row.size() != m) throw std::invalid_argument("mul_plain_sum_batches: bad operand lists");
+        for (auto *pt : row)
+            if (pt->level != level) throw std::invalid_argument("mul_plain_sum_batches: level mismatch");
+    }
+    if (level >= I.P.L) throw std::runtime_error("mul_plain_sum_batches: no levels left");
+    if (!stack_masks_enabled()) {
+        std::vector<CtPtr> T;
+        std::vector<const Ciphertext *> tp;
+        for (auto &row : p) {
+            T.push_back(mul_plain_sum(a, row));
+            tp.push_back(T.back().get());
+        }
+        return stack(tp);
+    }
+    const size_t nn = n(), ell = a[0]->limbs;
+    for (int b = 0; b < nb; ++b) {  // what nb mul_plain_sum calls book
+        ctr.ptmult += m;
+        ctr.rescale += 1;
+        count_bytes(2.0 * ell * m + 2.0 * ell, 1);
+        count_bytes((double)ell * m, 1);
+    }
+    std::vector<const u64 *> cp, pp;
+    for (size_t i = 0; i < m; ++i) cp.push_back(a[i]->data);
+    for (auto &row : p)
+        for (auto *pt : row) pp.push_back(pt->data);
+    auto tm = I.alloc((size_t)2 * nb * ell * nn * 8);
+    u64 *t = static_cast<u64 *>(tm->p);
+    dev::ew_mul_plain_sum_batches(t, cp.data(), I.ptr_table(pp), (int)m, nb, (int)ell, ell * nn, MODS, LOGN, ST);
+    auto r = new_ct(level + 1, a[0]->slots, I.P.delta[level + 1], ell - 1, nb);
+    I.rescale(t, ell, ell * nn, 2 * nb, r->data);
+    return r;
+}
+
 // FHE_TENSOR_LIN (A/B, default 1): mul_add's summands folded into the tensor pass
 static bool tensor_lin_enabled() {
     static const int on = [] {
@@ -1557,6 +1643,17 @@ static bool tensor_lin_enabled() {
         return e ? std::atoi(e) : 1;
     }();
     return on != 0;
+}
+
+// FHE_MUL_FOLD_CONST (A/B, default 1): mul_add's a_const added on load in the
+// tensor pass and its out_const there as a term of d0; 0: the separate
+// add_const / add_const_inplace launches.  Same words either way.
+static bool mul_fold_const() {
+    static const bool on = [] {
+        const char *e = std::getenv("FHE_MUL_FOLD_CONST");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return on;
 }
 
 // ct x ct with relinearisation and rescale.  b may be a single ciphertext
@@ -1567,13 +1664,26 @@ CtPtr Engine::mul(const Ciphertext &a0, const Ciphertext &b0) { return mul_add(a
 // pre-rescale scale (the constants of linear_sum_to(xs, c, level+1)) and added
 // to the tensor's (d0, d1) before relinearisation (oracle: Context::mul_add).
 CtPtr Engine::mul_add(const Ciphertext &a0, const Ciphertext &b0, const std::vector<const Ciphertext *> &xs,
-                      const std::vector<double> &cs, const Ciphertext *raw, const Ciphertext *a_add) {
+                      const std::vector<double> &cs, const Ciphertext *raw, const Ciphertext *a_add, double a_const,
+                      double out_const) {
     auto &I = *impl;
     if (a0.batch != b0.batch && b0.batch != 1) throw std::invalid_argument("mul: batch size mismatch");
     // a + a_add fused into the tensor pass only where add() would not level-adjust
     // and the sum would not be level-adjusted against b; otherwise formed first
-    if (a_add && (a_add->level != a0.level || a_add->batch != a0.batch || a0.level < b0.level))
-        return mul_add(*add(a0, *a_add), b0, xs, cs, raw);
+    if (a_add && (a_add->level != a0.level || a_add->batch != a0.batch || a0.level < b0.level)) {
+        CtPtr s = add(a0, *a_add);
+        if (a_const != 0.0) s = add_const(*s, a_const);
+        return mul_add(*s, b0, xs, cs, raw, nullptr, 0.0, out_const);
+    }
+    // + a_const on load likewise only where add_const would see this operand
+    // (mul_fold_left); + out_const as a term of d0 unless switched off
+    if (a_const != 0.0 && !mul_fold_left(mul_fold_const(), a0.level, b0.level))
+        return mul_add(*add_const(a0, a_const), b0, xs, cs, raw, a_add, 0.0, out_const);
+    if (out_const != 0.0 && !mul_fold_const()) {
+        CtPtr r = mul_add(a0, b0, xs, cs, raw, a_add, a_const, 0.0);
+        add_const_inplace(r, out_const);
+        return r;
+    }
     auto a = std::make_shared<Ciphertext>(a0), b = std::make_shared<Ciphertext>(b0);
     match_levels(a, b);
     if (a->level >= I.P.L) throw std::runtime_error("mul: no levels left");
@@ -1587,6 +1697,11 @@ CtPtr Engine::mul_add(const Ciphertext &a0, const Ciphertext &b0, const std::vec
     auto d01m = I.alloc((size_t)B * 2 * ell * nn * 8), d2m = I.alloc((size_t)B * ell * nn * 8);
     u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
     if (a_add) count_bytes(6.0 * ell, B);  // the add it replaces
+    // the constant steps they replace: add_const's copy, add_const_inplace's c0 pass
+    const host::SConst Ka = a_const != 0.0 ? host::const_at_scale(a_const, a->scale) : host::SConst{};
+    const host::SConst Ko = out_const != 0.0 ? host::const_at_scale(out_const, I.P.delta[a->level + 1]) : host::SConst{};
+    if (a_const != 0.0) count_bytes(4.0 * ell, B);
+    if (out_const != 0.0) count_bytes(2.0 * (ell - 1), B);
     // the summands folded into the tensor pass (k_tensor_lin) when they share a
     // limb count and are at most four: no second pass over d01
     bool fused_lin = false;
@@ -1610,12 +1725,26 @@ CtPtr Engine::mul_add(const Ciphertext &a0, const Ciphertext &b0, const std::vec
             fused_lin = dev::ew_tensor_lin(d01, d2, a->data, b->data, (int)ell, B, 2 * ell * nn,
                                            b->batch == 1 ? 0 : 2 * ell * nn, x.data(), k.data(), sh.data(),
                                            (int)x.size(), xs[0]->limbs * nn, MODS, LOGN, ST,
-                                           a_add ? a_add->data : nullptr, 2 * ell * nn);
+                                           a_add ? a_add->data : nullptr, 2 * ell * nn, Ka.k, Ka.sh, Ko.k, Ko.sh);
         if (fused_lin) ctr.constmult += xs.size() * B;
     }
-    if (!fused_lin)
+    // a raw summand alone rides the tensor pass as a summand with constant one
+    // (mul_mod(x, 1) = x and the sum is reduced once: add_mod's words) instead of
+    // a k_add pass over d01 behind it
+    bool fused_raw = false;
+    if (raw && (raw->level != a->level || raw->limbs != ell || raw->batch != B))
+        throw std::invalid_argument("mul_add: raw summand shape mismatch");
+    if (raw && xs.empty() && tensor_lin_enabled() && mul_fold_const()) {
+        const u64 *x = raw->data;
+        const int64_t k = 1;
+        const uint8_t sh = 0;
+        fused_raw = dev::ew_tensor_lin(d01, d2, a->data, b->data, (int)ell, B, 2 * ell * nn,
+                                       b->batch == 1 ? 0 : 2 * ell * nn, &x, &k, &sh, 1, ell * nn, MODS, LOGN, ST,
+                                       a_add ? a_add->data : nullptr, 2 * ell * nn, Ka.k, Ka.sh, Ko.k, Ko.sh);
+    }
+    if (!fused_lin && !fused_raw)
         dev::ew_tensor(d01, d2, a->data, b->data, (int)ell, B, 2 * ell * nn, b->batch == 1 ? 0 : 2 * ell * nn, MODS,
-                       LOGN, ST, a_add ? a_add->data : nullptr, 2 * ell * nn);
+                       LOGN, ST, a_add ? a_add->data : nullptr, 2 * ell * nn, Ka.k, Ka.sh, Ko.k, Ko.sh);
     if (!xs.empty() && !fused_lin) {
         const int target = a->level + 1;
         const u64 qd = I.P.primes[I.P.L - target + 1];
@@ -1639,9 +1768,7 @@ CtPtr Engine::mul_add(const Ciphertext &a0, const Ciphertext &b0, const std::vec
                                ell * nn, kv.first * nn, MODS, LOGN, ST, true, kv.second.sh.data());
         ctr.constmult += xs.size() * B;
     }
-    if (raw) {
-        if (raw->level != a->level || raw->limbs != ell || raw->batch != B)
-            throw std::invalid_argument("mul_add: raw summand shape mismatch");
+    if (raw && !fused_raw) {
         const size_t ln = ell * nn;
         dev::ew_add(d01, d01, raw->data, (int)ell, 2 * B, dev::Seg{ln, ln, ln}, MODS, LOGN, ST);
     }
@@ -1651,8 +1778,9 @@ CtPtr Engine::mul_add(const Ciphertext &a0, const Ciphertext &b0, const std::vec
     I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
     return r;
 }
-CtPtr Engine::mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add) {
-    return mul_add(a, b, {}, {}, &raw, a_add);
+CtPtr Engine::mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add,
+                          double a_const, double out_const) {
+    return mul_add(a, b, {}, {}, &raw, a_add, a_const, out_const);
 }
 CtPtr Engine::square(const Ciphertext &a) { return mul(a, a); }
 

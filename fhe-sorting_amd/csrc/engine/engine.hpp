@@ -207,10 +207,27 @@ class Engine {
     // a*b + sum_i c_i x_i with one rescale (lazy rescaling of PS remainders)
     // a_add (optional): the left operand is a + a_add, formed inside the tensor
     // pass (same words as add(a, a_add) first)
+    // a_const (0 = none): a constant at a's scale added to the left operand after
+    // a_add, on load in the tensor pass (the words of add_const(add(a, a_add), c));
+    // out_const (0 = none): a constant at the result's scale, added to d0 in the
+    // tensor pass times the prime the rescale drops (the HMult tail is linear in
+    // d0 and divides by that prime: the words of add_const on the product).  FHE_MUL_FOLD_CONST=0 or
+    // an operand that is level-adjusted first takes the separate launches.
     CtPtr mul_add(const Ciphertext &a, const Ciphertext &b, const std::vector<const Ciphertext *> &xs,
-                  const std::vector<double> &cs, const Ciphertext *raw = nullptr, const Ciphertext *a_add = nullptr);
+                  const std::vector<double> &cs, const Ciphertext *raw = nullptr, const Ciphertext *a_add = nullptr,
+                  double a_const = 0.0, double out_const = 0.0);
+    // whether mul_add forms a + a_const on load: only where add_const would see
+    // the operand the tensor loads, i.e. a is not level-adjusted against b
+    static bool mul_fold_left(bool enabled, int a_level, int b_level) { return enabled && a_level >= b_level; }
+    // the masked sums of nb batches over one list of ciphertexts in one pass:
+    // member b of the result is mul_plain_sum(a, p[b]) word for word (one kernel
+    // over all batches, one rescale of the 2 nb segments).  Every a_i is a single
+    // ciphertext; FHE_RANK_STACK_MASKS=0 runs the nb sums and stacks them.
+    CtPtr mul_plain_sum_batches(const std::vector<const Ciphertext *> &a,
+                                const std::vector<std::vector<const Plaintext *>> &p);
     // same with the sum already formed: raw = linear_sums_to(xs, {c}, level+1, false)[0]
-    CtPtr mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add = nullptr);
+    CtPtr mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add = nullptr,
+                      double a_const = 0.0, double out_const = 0.0);
     // the stack a (B members) times each of P single ciphertexts: member p B + z
     // of the result is mul(member(a, z), *cols[p]) word for word.  One tensor pass
     // (k_tensor_cols), then mul's relinearisation / rescale tail on P B members.

@@ -106,6 +106,8 @@ _SIGS = {
     'fhe_mul_relin': (C.c_int, [vp, vp, vp, PP]),
     'fhe_square_relin': (C.c_int, [vp, vp, PP]),
     'fhe_mul_add': (C.c_int, [vp, vp, vp, PP, dp, C.c_int, vp, vp, PP]),
+    'fhe_mul_add_const': (C.c_int, [vp, vp, vp, PP, dp, C.c_int, vp, vp, C.c_double, C.c_double, PP]),
+    'fhe_mul_fold_left': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'fhe_rotate': (C.c_int, [vp, vp, C.c_int, PP]),
     'fhe_rotate_hoisted': (C.c_int, [vp, vp, ip, C.c_int, PP]),
     'fhe_linear_sum_to': (C.c_int, [vp, PP, dp, C.c_int, C.c_int, PP]),
@@ -200,6 +202,10 @@ _SIGS = {
     'fhe_ct_stack': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_mul_plain_sum': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
                                     C.POINTER(C.c_void_p)]),
+    'fhe_mul_plain_sum_batches': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int,
+                                            C.POINTER(C.c_void_p)]),
+    'fhe_plain_sum_tile': (C.c_int, []),
+    'fhe_plain_sum_batches_limb_units': (C.c_double, [C.c_int, C.c_int, C.c_int]),
     'fhe_ct_member': (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_ct_sum_members': (C.c_int, [vp, vp, C.POINTER(C.c_void_p)]),
     'fhe_kernel_clock_stop': (C.c_int, [vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -671,6 +677,14 @@ class Context:
         c = np.ascontiguousarray(cs, dtype=np.float64)
         return self._new(lib().fhe_mul_add, a.h, b.h, arr, _dbl(c), len(xs), None if raw is None else raw.h,
                          None if a_add is None else a_add.h)
+
+    def mul_add_const(self, a, b, xs=(), cs=(), raw=None, a_add=None, a_const=0.0, out_const=0.0):
+        """mul_add with (a [+ a_add] + a_const) as the left operand and out_const added to the
+        result: the words of add_const before and after the product, formed inside its passes"""
+        arr = (C.c_void_p * max(1, len(xs)))(*[x.h for x in xs])
+        c = np.ascontiguousarray(cs, dtype=np.float64)
+        return self._new(lib().fhe_mul_add_const, a.h, b.h, arr, _dbl(c), len(xs), None if raw is None else raw.h,
+                         None if a_add is None else a_add.h, float(a_const), float(out_const))
     def rotate(self, a, k): return self._new(lib().fhe_rotate, a.h, k)
 
     def rotate_hoisted(self, a, ks):
@@ -690,6 +704,17 @@ class Context:
         pa = (C.c_void_p * len(pts))(*[p.h for p in pts])
         out = C.c_void_p()
         _chk(lib().fhe_mul_plain_sum(self.h, ca, pa, len(cts), C.byref(out)))
+        return Ct(self, out.value)
+
+    def mul_plain_sum_batches(self, cts, pts_per_batch):
+        """stack of mul_plain_sum(cts, pts) over the batches' plaintext lists, in one pass"""
+        m, nb = len(cts), len(pts_per_batch)
+        if any(len(r) != m for r in pts_per_batch):
+            raise ValueError('mul_plain_sum_batches: one plaintext per ciphertext in every batch')
+        ca = (C.c_void_p * m)(*[c.h for c in cts])
+        pa = (C.c_void_p * (m * nb))(*[p.h for r in pts_per_batch for p in r])
+        out = C.c_void_p()
+        _chk(lib().fhe_mul_plain_sum_batches(self.h, ca, pa, m, nb, C.byref(out)))
         return Ct(self, out.value)
 
     def member(self, a, m): return self._new(lib().fhe_ct_member, a.h, m)

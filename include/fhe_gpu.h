@@ -120,6 +120,18 @@ int fhe_ct_free(fhe_ct *ct);
  * blindRotationOptN (src/sort_algo.h:341-346, 573-577; OpenFHE FLEXIBLEAUTO
  * rescales the sum lazily).  All operands at one level; cts share a batch. */
 int fhe_mul_plain_sum(fhe_ctx *ctx, const fhe_ct *const *cts, const fhe_pt *const *pts, int m, fhe_ct **out);
+/* The masked sums of `nb` batches over one list of `m` single ciphertexts (the
+ * comparator batches of a DirectSort chunk share their baby steps): member b of
+ * the result is fhe_mul_plain_sum(cts, pts + b * m, m) word for word, formed by
+ * one kernel over every batch and one rescale.  pts: nb * m handles, batch-major.
+ * FHE_RANK_STACK_MASKS=0 runs the nb sums and stacks them. */
+int fhe_mul_plain_sum_batches(fhe_ctx *ctx, const fhe_ct *const *cts, const fhe_pt *const *pts, int m, int nb,
+                              fhe_ct **out);
+/* batches a thread of that kernel keeps, and the limbs of n words one pass over
+ * nb batches of m terms moves with that tile: 2 m ceil(nb / tile) + m nb + 2 nb
+ * (nb (3 m + 2) for nb separate sums); < 0 for a tile < 1 */
+int fhe_plain_sum_tile(void);
+double fhe_plain_sum_batches_limb_units(int m, int nb, int tile);
 /* ciphertext batches: `m` ciphertexts at one level stacked into one handle of
  * batch sum(batch_i) ([batch][2][limbs][n]); every op applies member-wise in
  * the same kernel launches (the reference loops over batches instead:
@@ -171,6 +183,15 @@ int fhe_square_relin(fhe_ctx *ctx, const fhe_ct *a, fhe_ct **out);
    is; a_add (or NULL) a ciphertext of a's level and batch added to a first */
 int fhe_mul_add(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *const *xs, const double *c, int m,
                 const fhe_ct *raw, const fhe_ct *a_add, fhe_ct **out);
+/* fhe_mul_add with two constants: (a [+ a_add] + a_const) * b + ... + out_const.  a_const is
+   at a's scale and added on load in the tensor pass, out_const at the result's scale and added
+   there as a term of d0 (times the prime the rescale drops, on the limbs below it): the words
+   of fhe_add_const before and after the product (0 = none).
+   FHE_MUL_FOLD_CONST=0, or an a below b's level, takes those separate steps instead. */
+int fhe_mul_add_const(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *b, const fhe_ct *const *xs, const double *c, int m,
+                      const fhe_ct *raw, const fhe_ct *a_add, double a_const, double out_const, fhe_ct **out);
+/* whether a_const is folded (1) or formed first (0) for operands at these levels */
+int fhe_mul_fold_left(int enabled, int a_level, int b_level);
 /* EvalRotate(ct, k) (src/rotation.h:224,231); FHE_ENOKEY if k has no key */
 int fhe_rotate(fhe_ctx *ctx, const fhe_ct *a, int k, fhe_ct **out);
 /* EvalFastRotationPrecompute + EvalFastRotation (src/rotation.h:281,342-346) */

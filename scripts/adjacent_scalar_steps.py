@@ -29,7 +29,7 @@ def is_tail(n):  # the closing row pass of a product (either class launch)
 
 
 def is_tensor(n):
-    return n == 'k_tensor' or n.startswith('k_tensor_lin<')
+    return n in ('k_tensor', 'k_tensor_c') or n.startswith('k_tensor_lin<') or n.startswith('k_tensor_lin_c<')
 
 
 def report(label, idx):
@@ -49,3 +49,7 @@ c = report('k_c0_op directly behind a closing row pass (+ const after a product,
 report('k_add directly behind a closing row pass (not a fold the design names; for the record)',
        [i for i, n in enumerate(names) if i and n == 'k_add' and is_tail(names[i - 1])])
 print(f'upper bound of both folds (every such launch removed at no cost): {(a + b + c) / 1e6:.3f} ms')
+t = sum(dur[i] for i in range(1, len(names)) if names[i] == 'k_add' and is_tensor(names[i - 1]))
+k = sum(1 for i in range(1, len(names)) if names[i] == 'k_add' and is_tensor(names[i - 1]))
+print(f"k_add directly behind k_tensor / k_tensor_lin (mul_add's raw summand): {k} launches, {t / 1e6:.3f} ms of "
+      f'{total / 1e6:.2f} ms, {len(rows)} dispatches')
