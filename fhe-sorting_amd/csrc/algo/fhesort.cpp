@@ -1145,6 +1145,18 @@ SortShape checkShape(int N, int max_batch) {
     s.np = check_np(N);
     return s;
 }
+int selectLayout(int N, int num_slots, int k, std::vector<int> *member, std::vector<int> *start) {
+    const int cap = Engine::select_cap(N, num_slots);
+    if (k < 1 || k > N) throw std::invalid_argument("select: the target count must lie in 1..N");
+    if (member) member->resize(k);
+    if (start) start->resize(k);
+    for (int p = 0; p < k; ++p) {
+        const int z = p / cap, q = p % cap;
+        if (member) (*member)[p] = z;
+        if (start) (*start)[p] = (int)(((long long)q * (N + 1) + (long long)z * cap) % num_slots);
+    }
+    return (k + cap - 1) / cap;
+}
 
 namespace {
 std::vector<double> mask_vector(int num_slots, int N, int k) {  // src/sort_algo.h:206-233
@@ -1667,6 +1679,123 @@ std::vector<CtPtr> DirectSortN::sortColumns(const Ciphertext &key, const std::ve
     if (!cache_masks) refresh_masks();
     CtPtr rank = constructRank(key, f, cfg);
     return rotationIndexCheckColumns(*rank, cols);
+}
+
+// Order statistics by encrypted rank.  Slot j of sorted output is
+// sum_i x_i delta(rank_i - j); rotationIndexCheckN reaches every j by rotating x,
+// here a window of N slots is given to one target j instead: the window holds
+// every rank_i once (the rank repeats with period N), so j - rank on it, the
+// sort's series and scaling, the product with x and the window's sum give the
+// order statistic, which the pick plaintext K keeps at the window's first slot
+// and the sort's fold moves to slot p (the window starts at p mod N).
+std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &rank, const std::vector<const Ciphertext *> &cols,
+                                              const std::vector<int> &targets) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)cols.size(), k = (int)targets.size();
+    if (P < 1) throw std::invalid_argument("select: no columns");
+    if (k < 1 || k > N)
+        throw std::invalid_argument("select: " + std::to_string(k) + " targets, need 1.." + std::to_string(N));
+    for (int p = 0; p < k; ++p)
+        if (targets[p] < 0 || targets[p] >= N)
+            throw std::invalid_argument("select: target " + std::to_string(p) + " (" + std::to_string(targets[p]) +
+                                        ") is outside [0, " + std::to_string(N) + ")");
+    const int series_level = indexSeriesLevel(rank.level);
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("select: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument("select: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->level > series_level)
+            throw std::runtime_error("select: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the series output (level " +
+                                     std::to_string(series_level) + "): no levels left to meet it");
+    }
+    const int cap = Engine::select_cap(N, s.num_slots), Z = (k + cap - 1) / cap;
+    const int level_c = rank.level, level_k = series_level + 1;
+    // every member's {C, K}: cached per (its targets, member, levels); with the
+    // cache off this call's own are encoded again here
+    std::vector<std::array<PtPtr, 2>> pts(Z);
+    for (int z = 0; z < Z; ++z) {
+        std::vector<int> tz(targets.begin() + z * cap, targets.begin() + std::min(k, (z + 1) * cap));
+        auto key = std::make_tuple(std::move(tz), z, level_c, level_k);
+        auto it = select_cache.find(key);
+        if (it == select_cache.end() || !cache_masks) {
+            if (select_cache.size() >= 1024) select_cache.clear();
+            it = select_cache.insert_or_assign(key, cc.encode_select(targets, z, s.num_slots, N, level_c, level_k)).first;
+        }
+        pts[z] = it->second;
+    }
+    Ciphertext rk = rank;
+    rk.slots = s.num_slots;
+    // every column brought once to the level the product meets it at, as
+    // rotationIndexCheckColumns does
+    std::vector<CtPtr> xs(P);
+    std::vector<const Ciphertext *> xp(P);
+    for (int p = 0; p < P; ++p) {
+        xs[p] = cc.level_adjust(*cols[p], series_level);
+        xs[p]->slots = s.num_slots;
+        xp[p] = xs[p].get();
+    }
+    const std::vector<double> &coeffs = sincCoefficients();
+    int logn = 0;
+    while ((1 << logn) < N) ++logn;
+    // members per stacked pass: max_stack, within the column product's member bound
+    const int chunk = std::max(1, std::min(std::max(1, max_stack), std::max(1, max_col_members) / P));
+    std::vector<CtPtr> parts;  // per chunk: the window sums, member c zc + (z - z0)
+    std::vector<int> part_members;
+    {
+        AlgoPhase ph("select_members");
+        for (int z0 = 0; z0 < Z; z0 += chunk) {
+            const int zc = std::min(chunk, Z - z0);
+            CtPtr d;
+            if (zc == 1) {
+                d = cc.plain_sub(*pts[z0][0], rk);
+            } else {  // C_z - rank = -(rank - C_z), exact mod q: the differences of the chunk as one stack
+                std::vector<const Plaintext *> cs;
+                for (int z = z0; z < z0 + zc; ++z) cs.push_back(pts[z][0].get());
+                d = cc.negate(*cc.sub_plain_stacked(rk, cs));
+            }
+            CtPtr r = evalChebyshevSeriesPS(cc, *cc.mul_const(*d, 1.0 / N / 2), coeffs, -1.0, 1.0);
+            d.reset();
+            if (r->level != series_level) throw std::logic_error("select: unexpected series output level");
+            CtPtr v = cc.mul_columns(*r, xp);
+            r.reset();
+            for (int i = 0; i < logn; ++i) v = cc.add(*v, *rot.rotate(*v, 1 << i));
+            parts.push_back(v);
+            part_members.push_back(zc);
+        }
+    }
+    AlgoPhase ph("select_fold");
+    CtPtr all = parts[0];
+    if (parts.size() > 1) {  // column-major over every member: c Z + z
+        std::vector<CtPtr> views;
+        std::vector<const Ciphertext *> vp;
+        for (int c = 0; c < P; ++c)
+            for (size_t h = 0; h < parts.size(); ++h)
+                for (int z = 0; z < part_members[h]; ++z) {
+                    views.push_back(cc.member(*parts[h], c * part_members[h] + z));
+                    vp.push_back(views.back().get());
+                }
+        all = cc.stack(vp);
+    }
+    parts.clear();
+    std::vector<const Plaintext *> ks;
+    for (int z = 0; z < Z; ++z) ks.push_back(pts[z][1].get());
+    CtPtr out = cc.mul_plain_sum_groups(*all, ks, P);
+    all.reset();
+    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+        out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
+    std::vector<CtPtr> outs(P);
+    for (int p = 0; p < P; ++p) {
+        outs[p] = P == 1 ? out : cc.clone(*cc.member(*out, p));
+        outs[p]->slots = N;
+    }
+    return outs;
+}
+
+std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
+                                              const std::vector<int> &targets, SignFunc f, const SignConfig &cfg) {
+    if (!cache_masks) refresh_masks();
+    CtPtr rank = constructRank(key, f, cfg);
+    return selectColumns(*rank, cols, targets);
 }
 
 // Re-encodes every cached mask (the reference's per-use encoding,

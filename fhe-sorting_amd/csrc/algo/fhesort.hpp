@@ -177,6 +177,14 @@ void directSortSizeParameters(int N, int &multDepth, std::vector<int> &rotations
 void hybridSortSizeParameters(int N, int &multDepth, std::vector<int> &rotations);
 SortShape rankShape(int N, int max_batch);
 SortShape checkShape(int N, int max_batch);
+// Layout of an order-statistic select of k targets over num_slots = N P_ slots
+// (DirectSortN::selectColumns): cap = P_ - 1 targets per member (1 when P_ = 1);
+// target p belongs to member p / cap and owns the cyclic window of N slots from
+// start[p] = ((p % cap) (N + 1) + (p / cap) cap) mod num_slots on.  The windows of
+// one member are disjoint, start[p] = p mod N, and every window holds each
+// residue mod N once.  Returns the member count ceil(k / cap); member / start
+// (optional) receive k entries.  Throws std::invalid_argument on a bad shape.
+int selectLayout(int N, int num_slots, int k, std::vector<int> *member, std::vector<int> *start);
 
 // Sums a ciphertext's u64 limbs over ranks in place (device pointer, count
 // u64); the engine reduces mod q afterwards.  nullptr = single rank.
@@ -225,6 +233,28 @@ class DirectSortN {
     // constructRank(key), then rotationIndexCheckColumns
     std::vector<CtPtr> sortColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols, SignFunc f,
                                    const SignConfig &cfg);
+    // Order statistics: out[c] holds, at slot p < targets.size(), column c's value
+    // at the element whose rank is targets[p] (any order, repeats allowed), and 0
+    // in the other slots -- the project's own extension, not in the reference.
+    // One group of N slots is dedicated to each target (selectLayout; DESIGN.md
+    // "Order statistics"): the rank is subtracted from the target held constant on
+    // that window, the index check's doubled-sinc series is evaluated once per
+    // member (a ciphertext of num_slots = N P_ slots holds P_ - 1 targets), the
+    // result is multiplied into every column (Engine::mul_columns), each window is
+    // summed into its first slot by log2(N) rotations, the first slots of all
+    // members are picked and added with one rescale
+    // (Engine::mul_plain_sum_groups), and the sort's fold brings them to slot p.
+    // Members run stacked in chunks of max_stack on the context's engine; the
+    // words do not depend on the chunking.  Same depth and output level as the
+    // sort; a column deeper than the series output is refused before any work.
+    // Unsharded.  With tied keys the result mixes as the sort does
+    // (tests/tie_model.py).  cache_masks false: the call re-encodes its own
+    // plaintexts at its start.
+    std::vector<CtPtr> selectColumns(const Ciphertext &rank, const std::vector<const Ciphertext *> &cols,
+                                     const std::vector<int> &targets);
+    // constructRank(key), then selectColumns
+    std::vector<CtPtr> selectColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
+                                     const std::vector<int> &targets, SignFunc f, const SignConfig &cfg);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;
@@ -289,6 +319,8 @@ class DirectSortN {
     void refresh_masks();
     std::map<std::tuple<int, int, int, int, int>, PtPtr> mask_cache;
     std::mutex mask_mu;
+    // the select's {C, K} plaintexts per (targets of the member, member, level of C, level of K)
+    std::map<std::tuple<std::vector<int>, int, int, int>, std::array<PtPtr, 2>> select_cache;
     std::vector<int> rot_indices;
     std::vector<std::unique_ptr<Engine>> lane_eng;
     std::vector<std::unique_ptr<RotationComposerN>> lane_rot;

@@ -662,6 +662,95 @@ int fhe_ct_sum_member_groups(fhe_ctx *ctx, const fhe_ct *a, int groups, fhe_ct *
     });
 }
 
+int fhe_direct_select(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols, int ncols,
+                      const int32_t *targets, int ntargets, int N, const int32_t *rots, int nrot, int n, int dg, int df,
+                      fhe_ct **outs) {
+    if (outs)
+        for (int p = 0; p < ncols; ++p) outs[p] = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        NEED(outs);
+        if (!key && !rank) throw std::invalid_argument("fhe_direct_select: neither a key nor a rank given");
+        if (ncols < 1 || !cols) throw std::invalid_argument("fhe_direct_select: ncols must be >= 1");
+        const Ciphertext &packing = rank ? *rank->p : *key->p;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            const std::string which = "fhe_direct_select: column " + std::to_string(p);
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
+            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (cols[p]->p->slots != packing.slots)
+                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the " +
+                                            (rank ? "rank " : "key ") + std::to_string(packing.slots));
+            v.push_back(cols[p]->p.get());
+        }
+        if (ntargets < 1 || ntargets > N || !targets)
+            throw std::invalid_argument("fhe_direct_select: ntargets must lie in 1.." + std::to_string(N));
+        for (int p = 0; p < ntargets; ++p)
+            if (targets[p] < 0 || targets[p] >= N)
+                throw std::invalid_argument("fhe_direct_select: target " + std::to_string(p) + " (" +
+                                            std::to_string(targets[p]) + ") is outside [0, " + std::to_string(N) + ")");
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = 0;  // selection is unsharded; a sharded caller passes the reduced rank in
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        const std::vector<int> t(targets, targets + ntargets);
+        // the depth refusal (a column below the series output) is raised by the
+        // select before it starts any work on the columns
+        std::vector<CtPtr> r = rank ? ds.selectColumns(*rank->p, v, t)
+                                    : ds.selectColumns(*key->p, v, t, SignFunc::CompositeSign, cfgof(n, dg, df));
+        for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
+    });
+}
+int fhe_select_layout(int N, int num_slots, int ntargets, int32_t *member, int32_t *start, int max) {
+    int count = -1;
+    int rc = guard([&] {
+        std::vector<int> m, s;
+        count = selectLayout(N, num_slots, ntargets, &m, &s);
+        for (int p = 0; p < ntargets && p < max; ++p) {
+            if (member) member[p] = m[p];
+            if (start) start[p] = s[p];
+        }
+    });
+    return rc == FHE_OK ? count : -rc;
+}
+int fhe_pt_encode_select(fhe_ctx *ctx, const int32_t *targets, int ntargets, int member, int num_slots, int N,
+                         int level_c, int level_k, fhe_pt **out) {
+    if (out) out[0] = out[1] = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        NEED(targets);
+        NEED(out);
+        if (ntargets < 1) throw std::invalid_argument("fhe_pt_encode_select: ntargets must be >= 1");
+        auto pts = ctx->eng->encode_select(std::vector<int>(targets, targets + ntargets), member, num_slots, N, level_c,
+                                           level_k);
+        out[0] = new fhe_pt{pts[0]};
+        out[1] = new fhe_pt{pts[1]};
+    });
+}
+int fhe_mul_plain_sum_groups(fhe_ctx *ctx, const fhe_ct *stack, const fhe_pt *const *pts, int npts, int groups,
+                             fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(stack);
+        NEED(pts);
+        NEED(out);
+        if (npts < 1) throw std::invalid_argument("fhe_mul_plain_sum_groups: npts must be >= 1");
+        std::vector<const Plaintext *> p;
+        for (int i = 0; i < npts; ++i) {
+            NEED(pts[i]);
+            p.push_back(pts[i]->p.get());
+        }
+        *out = wrap(ctx->eng->mul_plain_sum_groups(*stack->p, p, groups));
+    });
+}
+
 int fhe_sort_hybrid(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, const int32_t *rots, int nrot, int n,
                     int dg, int df, int mode, int max_array, int mask_mode, int shard_rank, int shard_world,
                     fhe_allreduce_fn fn, void *user, fhe_ct **out) {

@@ -17,7 +17,8 @@
 //
 // The sort's public masks are generated on the device too (kernel k_mask_slots:
 // mask_vector(k) rotated by r, checking_vector(k), src/sort_algo.h:206-233,
-// 272-286), so a batch of masks needs no host-to-device copy of slot values.
+// 272-286), so a batch of masks needs no host-to-device copy of slot values;
+// so are the target / pick vectors of the order-statistic select (k_select_slots).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -118,6 +119,22 @@ __global__ __launch_bounds__(256) void k_mask_slots(double2 *v, int S, int N, co
     v[t] = make_double2(val, 0.0);
 }
 
+// select plaintexts of one member (order statistics): window q < cnt
+// is the N slots from (q (N + 1) + shift) mod S on.  vc[i] = t[q] on window q,
+// vk[i] = 1 at the first slot of window q, both 0 elsewhere.  One thread per
+// slot of the pair; the windows lie inside [0, cnt (N + 1)) after the shift, so
+// q and the position in the window come from one division.
+__global__ __launch_bounds__(256) void k_select_slots(double2 *vc, double2 *vk, int S, int N, const int *t, int cnt,
+                                                      int shift) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S) return;
+    const int j = (i - shift % S + S) % S;
+    const int q = j / (N + 1), r = j % (N + 1);
+    const bool in = q < cnt && r < N;
+    vc[i] = make_double2(in ? (double)t[q] : 0.0, 0.0);
+    vk[i] = make_double2(in && r == 0 ? 1.0 : 0.0, 0.0);
+}
+
 }  // namespace
 
 void encode_ifft(double2 *v, int64_t *coef, int B, int S, int n, const double2 *ksi, const uint32_t *rot,
@@ -142,6 +159,12 @@ void mask_slots(double2 *v, int B, int S, int N, const int *spec, hipStream_t st
     const size_t total = (size_t)B * S;
     if (!total) return;
     hipLaunchKernelGGL(k_mask_slots, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, v, S, N, spec, total);
+}
+
+void select_slots(double2 *vc, double2 *vk, int S, int N, const int *targets, int count, int shift, hipStream_t st) {
+    if (S <= 0) return;
+    launch_clocked("k_select_slots", 2.0 * S * sizeof(double2), k_select_slots, dim3((unsigned)((S + 255) / 256)),
+                   dim3(256), st, vc, vk, S, N, targets, count, shift);
 }
 
 }  // namespace dev

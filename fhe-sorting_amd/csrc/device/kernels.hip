@@ -1279,6 +1279,71 @@ __global__ __launch_bounds__(NT) void k_mul_plain_sum_batches(u64 *out, PlainSum
         }
 }
 
+// k_mul_plain_sum for G groups of m stacked members against one list of m
+// plaintexts (the select's pick sums, one group per column):
+// out[2 g + c] = sum_z in[g mtot + base + z][c] * pt[z]  (accumulate: + out), g < G.
+// The plaintexts are the same for every group, so a thread keeps the 2 x 2 sums
+// of PSG_TG groups, loads each plaintext pair of words once per tile and applies
+// it to the tile's members: 2 m G + m ceil(G / TG) + 2 G limb-units against
+// G (3 m + 2).  The sums are exact, so the words are k_mul_plain_sum's.  A last
+// tile narrower than PSG_TG repeats its last group and stores only the valid ones.
+// grid: x = coefficient block, y = limb, z = group tile (k_sum_member_groups' shape).
+constexpr int PSG_TG = 4;
+struct PlainSumGroupArgs {
+    const u64 *pt[LIN_MAX];
+    int m, base, mtot, G, accumulate;
+};
+__global__ __launch_bounds__(NT) void k_mul_plain_sum_groups(u64 *out, const u64 *in, PlainSumGroupArgs A,
+                                                             size_t ln_all, const Mod *mods, int logN) {
+    constexpr int TG = PSG_TG;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod md = mods[l];
+    const size_t lo = (size_t)l * n + k;
+    const int g0 = blockIdx.z * TG;
+    const u64 *src[TG];  // member `base` of the tile's groups (block-uniform)
+#pragma unroll
+    for (int t = 0; t < TG; ++t) src[t] = in + ((size_t)min(g0 + t, A.G - 1) * A.mtot + A.base) * 2 * ln_all + lo;
+    Acc128 r[TG][2][2];
+    if (A.accumulate) {
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const ulonglong2 v = ld2(out + (size_t)(2 * min(g0 + t, A.G - 1) + c) * ln_all + lo);
+                r[t][c][0].lo = v.x;
+                r[t][c][1].lo = v.y;
+            }
+    }
+#pragma unroll 1
+    for (int i = 0; i < A.m; ++i) {
+        const ulonglong2 p = ld2(A.pt[i] + lo);
+        ulonglong2 x0[TG], x1[TG];
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            x0[t] = ld2(src[t] + (size_t)i * 2 * ln_all);
+            x1[t] = ld2(src[t] + (size_t)i * 2 * ln_all + ln_all);
+        }
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+            mac128(r[t][0][0], x0[t].x, p.x);
+            mac128(r[t][0][1], x0[t].y, p.y);
+            mac128(r[t][1][0], x1[t].x, p.x);
+            mac128(r[t][1][1], x1[t].y, p.y);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < TG; ++t)
+        if (g0 + t < A.G) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                st2(out + (size_t)(2 * (g0 + t) + c) * ln_all + lo,
+                    make_ulonglong2(reduce128(r[t][c][0], md), reduce128(r[t][c][1], md)));
+        }
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3067,6 +3132,25 @@ void ew_mul_plain_sum_batches(u64 *out, const u64 *const *cts, const u64 *const 
             launch_clocked("k_mul_plain_sum_batches", B, k_mul_plain_sum_batches, dim3(g0.z, g0.x, g0.y), dim3(NT), st,
                            out, A, seg, mods, logN);
         }
+    }
+}
+int plain_sum_groups_tile() { return PSG_TG; }
+void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int m, int groups, int limbs,
+                             const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || groups <= 0 || m <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    const int gtiles = (groups + PSG_TG - 1) / PSG_TG;
+    for (int base = 0; base < m; base += LIN_MAX) {
+        PlainSumGroupArgs A{};
+        A.m = std::min(LIN_MAX, m - base);
+        A.base = base;
+        A.mtot = m;
+        A.G = groups;
+        A.accumulate = base > 0;
+        for (int i = 0; i < A.m; ++i) A.pt[i] = pts[base + i];
+        const double B = 8.0 * (2.0 * A.m * groups + (double)A.m * gtiles + 2.0 * groups * (1 + A.accumulate)) * ln_all;
+        launch_clocked("k_mul_plain_sum_groups", B, k_mul_plain_sum_groups, ew_grid(logN, limbs, gtiles), dim3(NT), st,
+                       out, in, A, ln_all, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

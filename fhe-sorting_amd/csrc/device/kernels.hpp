@@ -250,6 +250,14 @@ int plain_sum_tile();
 double plain_sum_batches_limb_units(int m, int nb, int tile);
 void ew_mul_plain_sum_batches(u64 *out, const u64 *const *cts, const u64 *const *pts, int m, int nb, int limbs,
                               size_t cpoly, const Mod *mods, int logN, hipStream_t st);
+// The masked sums of `groups` groups of m stacked members against one list of m
+// plaintexts: out[2 g + c] = sum_z in[g m + z][c] * pts[z] (in: [groups m][2][limbs][n],
+// out segment stride limbs n).  A thread holds the sums of up to
+// plain_sum_groups_tile() groups and loads each plaintext once for all of them;
+// word for word one ew_mul_plain_sum per group.
+int plain_sum_groups_tile();
+void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int m, int groups, int limbs,
+                             const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);
@@ -276,6 +284,11 @@ void encode_ifft(double2 *v, int64_t *coef, int B, int S, int n, const double2 *
 // the sort's masks as slot values: spec [B][3] = {kind, k, r}: kind 0
 // mask_vector(S, N, k) rotated by r, kind 1 checking_vector(S, N, k)
 void mask_slots(double2 *v, int B, int S, int N, const int *spec, hipStream_t st);
+// the select's slot vectors of one member (DirectSortN::selectColumns): window
+// q < count is the N slots from (q (N + 1) + shift) mod S on; vc [S] holds
+// targets[q] (device array) on window q, vk [S] holds 1 at each window's first
+// slot, both 0 elsewhere.  Needs count (N + 1) - 1 <= S.
+void select_slots(double2 *vc, double2 *vk, int S, int N, const int *targets, int count, int shift, hipStream_t st);
 
 // ---------------------------------------------------------------- keyswitch
 // ext[m][j][t][k] for every member m, digit j and target t not in digit j

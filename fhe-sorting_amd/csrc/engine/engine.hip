@@ -1182,6 +1182,51 @@ std::vector<PtPtr> Engine::encode_masks(const std::vector<MaskSpec> &specs, int 
     return out;
 }
 
+int Engine::select_cap(int N, int num_slots) {
+    if (N < 1 || (N & (N - 1)) || num_slots < N || num_slots % N)
+        throw std::invalid_argument("select layout: N must be a power of two and num_slots a multiple of it");
+    const int parts = num_slots / N;
+    if ((parts & (parts - 1)) || parts > N)
+        throw std::invalid_argument("select layout: num_slots / N must be a power of two <= N");
+    return parts >= 2 ? parts - 1 : 1;
+}
+
+std::array<PtPtr, 2> Engine::encode_select(const std::vector<int> &targets, int member, int num_slots, int N,
+                                           int level_c, int level_k) {
+    auto &I = *impl;
+    const int cap = select_cap(N, num_slots);
+    if ((size_t)num_slots > I.n() / 2) throw std::invalid_argument("encode_select: slots must be a power of two <= n/2");
+    const int k = (int)targets.size();
+    if (k < 1 || k > N) throw std::invalid_argument("encode_select: the target count must lie in 1..N");
+    if (member < 0 || (long long)member * cap >= k) throw std::invalid_argument("encode_select: no such member");
+    for (int lv : {level_c, level_k})
+        if (lv < 0 || lv > I.P.L) throw std::invalid_argument("encode_select: level out of range");
+    const int first = member * cap, cnt = std::min(cap, k - first);
+    for (int q = 0; q < cnt; ++q)
+        if (targets[first + q] < 0 || targets[first + q] >= N)
+            throw std::invalid_argument("encode_select: target " + std::to_string(first + q) + " is outside [0, N)");
+    const u64 t0 = now_ns();
+    I.enc_tables();
+    // encode_sorted takes its members in level order
+    const int ic = level_c <= level_k ? 0 : 1, ik = 1 - ic;
+    std::vector<int> levels(2);
+    std::vector<double> scales(2);
+    levels[ic] = level_c;
+    levels[ik] = level_k;
+    scales[ic] = I.P.delta[level_c];
+    scales[ik] = I.P.delta[level_k];
+    auto vm = I.alloc((size_t)2 * num_slots * sizeof(double2));
+    double2 *v = static_cast<double2 *>(vm->p);
+    auto tm = I.alloc((size_t)cnt * 4);
+    HIP_OK(hipMemcpyAsync(tm->p, targets.data() + first, (size_t)cnt * 4, hipMemcpyHostToDevice, I.st));
+    dev::select_slots(v + (size_t)ic * num_slots, v + (size_t)ik * num_slots, num_slots, N,
+                      static_cast<const int *>(tm->p), cnt, first % num_slots, I.st);
+    auto sorted = I.encode_sorted(v, 2, num_slots, levels, scales);  // synchronises: `targets` outlives its copy
+    host_stats().encode_ns += now_ns() - t0;
+    host_stats().encodes += 2;
+    return {sorted[ic], sorted[ik]};
+}
+
 std::vector<PtPtr> Engine::encode_device(const std::vector<std::vector<double>> &vs, int slots,
                                          const std::vector<int> &levels) {
     auto &I = *impl;
@@ -1633,6 +1678,57 @@ CtPtr Engine::mul_plain_sum_batches(const std::vector<const Ciphertext *> &a,
     dev::ew_mul_plain_sum_batches(t, cp.data(), I.ptr_table(pp), (int)m, nb, (int)ell, ell * nn, MODS, LOGN, ST);
     auto r = new_ct(level + 1, a[0]->slots, I.P.delta[level + 1], ell - 1, nb);
     I.rescale(t, ell, ell * nn, 2 * nb, r->data);
+    return r;
+}
+
+// FHE_SELECT_FUSED (A/B, default 1): mul_plain_sum_groups' sums of every group in
+// one pass over the shared plaintexts; 0: one mul_plain_sum per group, stacked
+static bool select_fused_enabled() {
+    static const bool on = [] {
+        const char *e = std::getenv("FHE_SELECT_FUSED");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return on;
+}
+
+// member g = sum_z a[g Z + z] * p[z] with one rescale: `groups` mul_plain_sum
+// calls over the same plaintexts, word for word, with their counters and op bytes
+CtPtr Engine::mul_plain_sum_groups(const Ciphertext &a, const std::vector<const Plaintext *> &p, int groups) {
+    auto &I = *impl;
+    if (p.empty() || groups < 1 || groups > 32767 || (size_t)a.batch != p.size() * (size_t)groups)
+        throw std::invalid_argument("mul_plain_sum_groups: the stack is not `groups` groups of one member per plaintext");
+    const int level = a.level, Z = (int)p.size();
+    for (auto *pt : p)
+        if (!pt || pt->level != level) throw std::invalid_argument("mul_plain_sum_groups: level mismatch");
+    if (level >= I.P.L) throw std::runtime_error("mul_plain_sum_groups: no levels left");
+    if (!select_fused_enabled()) {
+        std::vector<CtPtr> T, views;
+        std::vector<const Ciphertext *> tp;
+        for (int g = 0; g < groups; ++g) {
+            std::vector<const Ciphertext *> ms;
+            for (int z = 0; z < Z; ++z) {
+                views.push_back(member(a, g * Z + z));
+                ms.push_back(views.back().get());
+            }
+            T.push_back(mul_plain_sum(ms, p));
+            tp.push_back(T.back().get());
+        }
+        return groups == 1 ? T[0] : stack(tp);
+    }
+    const size_t nn = n(), ell = a.limbs;
+    for (int g = 0; g < groups; ++g) {  // what `groups` mul_plain_sum calls book
+        ctr.ptmult += Z;
+        ctr.rescale += 1;
+        count_bytes(2.0 * ell * Z + 2.0 * ell, 1);
+        count_bytes((double)ell * Z, 1);
+    }
+    std::vector<const u64 *> pp;
+    for (auto *pt : p) pp.push_back(pt->data);
+    auto tm = I.alloc((size_t)2 * groups * ell * nn * 8);
+    u64 *t = static_cast<u64 *>(tm->p);
+    dev::ew_mul_plain_sum_groups(t, a.data, pp.data(), Z, groups, (int)ell, MODS, LOGN, ST);
+    auto r = new_ct(level + 1, a.slots, I.P.delta[level + 1], ell - 1, groups);
+    I.rescale(t, ell, ell * nn, 2 * groups, r->data);
     return r;
 }
 

@@ -171,6 +171,17 @@ class Engine {
     };
     std::vector<PtPtr> encode_masks(const std::vector<MaskSpec> &specs, int num_slots, int N);
     std::vector<PtPtr> encode_device(const std::vector<std::vector<double>> &vs, int slots, const std::vector<int> &levels);
+    // The two plaintexts of member `member` of an order-statistic select
+    // (DirectSortN::selectColumns; layout: select_layout): {C at level_c, K at
+    // level_k}.  C holds targets[p] on the window of every target p of the member,
+    // K holds 1 at each window's first slot, both 0 elsewhere.  The slot vectors
+    // are filled on the device (k_select_slots) from the member's targets; each
+    // plaintext equals encode() of its vector word for word.
+    std::array<PtPtr, 2> encode_select(const std::vector<int> &targets, int member, int num_slots, int N, int level_c,
+                                       int level_k);
+    // targets per member (cap) of that layout; throws unless N and num_slots / N
+    // are powers of two with num_slots / N <= N
+    static int select_cap(int N, int num_slots);
     CtPtr encrypt(const std::vector<double> &v, int slots, int level = 0);
     CtPtr encrypt_pt(const Plaintext &pt);
     // OpenFHE FLEXIBLEAUTOEXT-style encryption: one extra level absorbs the
@@ -225,6 +236,12 @@ class Engine {
     // ciphertext; FHE_RANK_STACK_MASKS=0 runs the nb sums and stacks them.
     CtPtr mul_plain_sum_batches(const std::vector<const Ciphertext *> &a,
                                 const std::vector<std::vector<const Plaintext *>> &p);
+    // the masked sums of `groups` groups of Z = p.size() consecutive members of
+    // the stack a against one plaintext list: member g of the result is
+    // mul_plain_sum({member(a, g Z + z)}_z, p) word for word (one kernel,
+    // k_mul_plain_sum_groups, over all groups, one rescale of the 2 `groups`
+    // segments).  FHE_SELECT_FUSED=0 (A/B): one mul_plain_sum per group, stacked.
+    CtPtr mul_plain_sum_groups(const Ciphertext &a, const std::vector<const Plaintext *> &p, int groups);
     // same with the sum already formed: raw = linear_sums_to(xs, {c}, level+1, false)[0]
     CtPtr mul_add_raw(const Ciphertext &a, const Ciphertext &b, const Ciphertext &raw, const Ciphertext *a_add = nullptr,
                       double a_const = 0.0, double out_const = 0.0);

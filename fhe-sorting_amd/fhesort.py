@@ -21,6 +21,7 @@ FHE_OK, FHE_EINVAL, FHE_ENOKEY, FHE_EDEPTH, FHE_EHIP, FHE_ENOMEM, FHE_EINTERNAL,
 NAF, BNAF, BINARY = 0, 1, 2
 SORT_COLUMN_MEMBERS_DEFAULT = 256  # fhe_set_sort_column_members' initial value (csrc/capi/capi.cpp)
 TENSOR_COLS_PER_THREAD = 4         # columns a k_tensor_cols thread owns (TC_PC, csrc/device/kernels.hip)
+PLAIN_SUM_GROUPS_PER_THREAD = 4    # groups a k_mul_plain_sum_groups thread owns (PSG_TG, csrc/device/kernels.hip)
 
 
 class FheError(RuntimeError):
@@ -131,6 +132,12 @@ _SIGS = {
     'fhe_set_sort_column_members': (C.c_int, [vp, C.c_int]),
     'fhe_mul_columns': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_ct_sum_member_groups': (C.c_int, [vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_direct_select': (C.c_int, [vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                    ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_select_layout': (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    'fhe_pt_encode_select': (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       PP]),
+    'fhe_mul_plain_sum_groups': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -776,6 +783,45 @@ class Context:
             hk.reraise(e)
         return [Ct(self, outs[i]) for i in range(len(cols))]
 
+    def direct_select(self, key, targets, N, rots, cfg, cols=None, rank=None):
+        """Order statistics by encrypted rank (fhe_direct_select): out[c] has N
+        slots, slot p < len(targets) holds cols[c]'s value at the element whose rank
+        is targets[p] (ranks 0..N-1, any order, repeats allowed), the other slots
+        hold zero.  cols=None: the key is the one column and its select is returned
+        (not a list).  rank=None: the rank is constructed from `key`; with a rank
+        (direct_sort mode 1), key may be None when cols are given.  Up to P_ - 1
+        targets (num_slots = N * P_) cost one index series on one ciphertext.  With
+        tied keys the result mixes values exactly as the sort does
+        (tests/tie_model.py): exact order statistics need distinct keys."""
+        r = np.asarray(rots, dtype=np.int32)
+        t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        single = cols is None
+        cols = [key] if single else list(cols)
+        arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
+        outs = (C.c_void_p * max(1, len(cols)))()
+        _chk(lib().fhe_direct_select(self.h, None if key is None else key.h, None if rank is None else rank.h, arr,
+                                     len(cols), t.ctypes.data_as(C.POINTER(C.c_int32)), len(t), N, _int(r), len(r),
+                                     cfg[0], cfg[1], cfg[2], outs))
+        res = [Ct(self, outs[i]) for i in range(len(cols))]
+        return res[0] if single else res
+
+    def encode_select(self, targets, member, num_slots, N, level_c, level_k):
+        """fhe_pt_encode_select: (C, K) of one member of a select, encoded on the device"""
+        t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        outs = (C.c_void_p * 2)()
+        _chk(lib().fhe_pt_encode_select(self.h, t.ctypes.data_as(C.POINTER(C.c_int32)), len(t), member, num_slots, N,
+                                        level_c, level_k, outs))
+        return Pt(self, outs[0]), Pt(self, outs[1])
+
+    def mul_plain_sum_groups(self, stack, pts, groups):
+        """member g = mul_plain_sum(members g * len(pts) .. of the stack, pts), all groups in one pass"""
+        pa = (C.c_void_p * max(1, len(pts)))(*[p.h for p in pts])
+        return self._new(lib().fhe_mul_plain_sum_groups, stack.h, pa, len(pts), groups)
+
+    @staticmethod
+    def select_layout(N, num_slots, ntargets):
+        return select_layout(N, num_slots, ntargets)
+
     def mul_columns(self, a, cols):
         """the stack a (B members) times each single ciphertext of cols: member
         p * B + z of the result is mul(member(a, z), cols[p]) word for word"""
@@ -1030,6 +1076,20 @@ def size_parameters(N):
     if m < 0:
         raise FheError(-m, lib().fhe_last_error().decode())
     return d.value, [int(x) for x in rots[:m]]
+
+
+def select_layout(N, num_slots, ntargets):
+    """fhe_select_layout (pure host): (members, member[p], start[p]) of a select of
+    ntargets targets over num_slots = N * P_ slots.  cap = P_ - 1 (1 when P_ = 1)
+    targets share a member; target p owns the cyclic window of N slots from
+    start[p] (= p mod N) on."""
+    k = max(1, int(ntargets))
+    member, start = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    m = lib().fhe_select_layout(N, num_slots, ntargets, member.ctypes.data_as(i32), start.ctypes.data_as(i32), k)
+    if m < 0:
+        raise FheError(-m, lib().fhe_last_error().decode())
+    return m, [int(x) for x in member], [int(x) for x in start]
 
 
 def mehp24_parameters(N):

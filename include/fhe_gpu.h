@@ -288,6 +288,54 @@ int fhe_set_sort_column_members(fhe_ctx *ctx, int max_members);
 int fhe_mul_columns(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *cols, int ncols, fhe_ct **out_stack);
 int fhe_ct_sum_member_groups(fhe_ctx *ctx, const fhe_ct *a, int groups, fhe_ct **out_stack);
 
+/* Order statistics by encrypted rank (the project's own extension, like
+ * fhe_direct_sort_columns; the reference has no such function).  targets[0 ..
+ * ntargets) are ranks in [0, N), in any order, repeats allowed, 1 <= ntargets <=
+ * N.  out[c] has N slots: slot p < ntargets holds cols[c]'s value at the element
+ * whose rank is targets[p], the other slots hold zero; the level is the sort's
+ * output level.  rank == NULL: constructRank(key) first; rank != NULL (what
+ * fhe_direct_sort mode 1 returns): key may be NULL.  Pass the key among cols for
+ * the k-th smallest key itself.  With num_slots = N P_ slots (the rank's shape)
+ * one ciphertext serves P_ - 1 targets (1 when P_ = 1), each on its own window
+ * of N slots (fhe_select_layout), so ntargets <= P_ - 1 cost one evaluation of the
+ * index series on one ciphertext instead of the sort's N / P_ stacked ones, and any
+ * ntargets cost ceil(ntargets / (P_ - 1)); the members run stacked in chunks of
+ * fhe_set_sort_stack, and the result does not depend on the chunking.
+ * Unsharded: a sharded caller builds the rank with fhe_direct_sort(mode 1,
+ * shard ...) and passes it in.  FHE_EINVAL (the message names the column) for
+ * ncols < 1, a null column, a column that is a stack, a column whose slot count
+ * differs from the rank's (or, without a rank, the key's); FHE_EINVAL for a
+ * missing key and rank, for ntargets outside 1..N and for a target outside
+ * [0, N) (the message names the first such target's index); FHE_EDEPTH for a
+ * column below the level of the series output.  On failure every output handle
+ * is NULL.  With tied keys the result mixes values exactly as the sort does
+ * (tests/tie_model.py): exact order statistics need distinct keys.  With
+ * fhe_set_mask_cache(ctx, 0) a call re-encodes its own plaintexts at its start. */
+int fhe_direct_select(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols, int ncols,
+                      const int32_t *targets, int ntargets, int N, const int32_t *rots, int nrot, int n, int dg,
+                      int df, fhe_ct **outs /* ncols handles */);
+/* pure host: the layout of such a select over num_slots = N P_ slots (N and P_
+ * powers of two, P_ <= N).  cap = P_ - 1 (1 when P_ = 1); target p belongs to
+ * member[p] = p / cap and owns the cyclic window of N slots from start[p] =
+ * ((p % cap) (N + 1) + member[p] cap) mod num_slots on, so start[p] = p mod N and
+ * the windows of one member are disjoint.  Writes min(ntargets, max) entries of
+ * each array (either may be NULL); returns the member count ceil(ntargets / cap),
+ * or -FHE_EINVAL. */
+int fhe_select_layout(int N, int num_slots, int ntargets, int32_t *member, int32_t *start, int max);
+/* for tests and bindings: the two plaintexts of member `member` of that select,
+ * generated and encoded on the device: out[0] (level_c) holds targets[p] on the
+ * window of every target p of the member, out[1] (level_k) holds 1 at the first
+ * slot of each of its windows, both 0 elsewhere; each equals fhe_pt_encode of
+ * that vector word for word. */
+int fhe_pt_encode_select(fhe_ctx *ctx, const int32_t *targets, int ntargets, int member, int num_slots, int N,
+                         int level_c, int level_k, fhe_pt **out /* 2 handles */);
+/* and its pick sums: `stack` holds groups * npts members, group-major; member g
+ * of the result is fhe_mul_plain_sum over members g npts .. g npts + npts - 1
+ * and pts, word for word, formed by one kernel over every group and one rescale
+ * (FHE_SELECT_FUSED=0: one fhe_mul_plain_sum per group, stacked). */
+int fhe_mul_plain_sum_groups(fhe_ctx *ctx, const fhe_ct *stack, const fhe_pt *const *pts, int npts, int groups,
+                             fhe_ct **out);
+
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
  * grows with it).  Results do not depend on it. */
