@@ -1394,6 +1394,11 @@ std::vector<CtPtr> DirectSortN::vecRotsOptMany(Lane L, const std::vector<CtPtr> 
 // compare(x, s_b) = ((sign(x - s_b) + 1) / 2); the per-batch results are summed
 // exactly mod q, so the rank equals the reference's batch-by-batch
 // accumulation (src/sort_algo.h:474-491) word for word.
+// tiebreak > 0: the public offset E_b (+eps where the compared
+// element is the element itself or precedes it, -eps where it follows) is added
+// to every difference before the sign, so equal values compare as their indices
+// do, no sign is taken at 0, and the closing constant is -1 (the self comparison
+// yields 1): the stable rank, at the same depth and levels.
 CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConfig &cfg) {
     const SortShape s = rankShape(N, max_batch);
     std::optional<AlgoPhase> ph;
@@ -1406,7 +1411,11 @@ CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConf
         if (b % shard_world == shard_rank) mine.push_back(b);
     CtPtr dup = cc.clone(x);
     dup->slots = s.num_slots;
-    cc.sync();  // baby steps and dup are read by every lane
+    // tie-breaking: the offsets E_b of this rank's batches, at the level the
+    // differences sit at (one masked sum's rescale below x)
+    std::map<int, PtPtr> offs;
+    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0]->level + 1);
+    cc.sync();  // baby steps, dup and the offsets are read by every lane
     const size_t chunk = (size_t)std::max(1, max_stack);
     auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
         Engine &E = *L.eng;
@@ -1418,7 +1427,14 @@ CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConf
             std::vector<const Ciphertext *> ptrs;
             for (auto &x : shifted) ptrs.push_back(x.get());
             // x - s_b of every batch written straight into the stacked ciphertext
-            CtPtr d = ptrs.size() == 1 ? E.sub(*dup, *shifted[0]) : E.sub_stacked(*dup, ptrs);
+            CtPtr d;
+            if (tiebreak > 0.0) {  // ... with E_b added in the same pass
+                std::vector<const Plaintext *> es;
+                for (int b : iss) es.push_back(offs.at(b).get());
+                d = E.sub_add_plain_stacked(*dup, ptrs, es);
+            } else {
+                d = ptrs.size() == 1 ? E.sub(*dup, *shifted[0]) : E.sub_stacked(*dup, ptrs);
+            }
             shifted.clear();
             CtPtr sg = sign(*d, E, f, cfg);
             E.add_const_inplace(sg, 1.0);
@@ -1437,8 +1453,36 @@ CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConf
     for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
         rank = cc.add(*rank, *rot.rotate(*rank, s.num_slots / (1 << i)));
     rank->slots = N;
-    cc.add_const_inplace(rank, -0.5);
+    // the self comparison: 1/2 at sign(0), a clean 1 with the tie-break offset
+    cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5);
     return rank;
+}
+
+// E_b of the given batches from the cache; the missing ones are encoded in one
+// device batch on the main engine.  cache_masks false: all of them are encoded
+// again (the select's rule for its own plaintexts).
+std::map<int, PtPtr> DirectSortN::tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level) {
+    std::map<int, PtPtr> out;
+    std::vector<int> missing;
+    for (int b : batches) {
+        auto it = tiebreak_cache.find(std::make_tuple(num_slots, b, level, tiebreak));
+        if (it != tiebreak_cache.end() && cache_masks)
+            out[b] = it->second;
+        else
+            missing.push_back(b);
+    }
+    if (missing.empty()) return out;
+    if (!cache_masks) {
+        cc.sync();
+        for (auto &e : lane_eng) e->sync();  // nothing of the last rank still reads the old ones
+    }
+    if (tiebreak_cache.size() + missing.size() > 1024) tiebreak_cache.clear();
+    auto pts = cc.encode_tiebreak(missing, num_slots, N, tiebreak, level);  // synchronises the main stream
+    for (size_t i = 0; i < missing.size(); ++i) {
+        tiebreak_cache.insert_or_assign(std::make_tuple(num_slots, missing[i], level, tiebreak), pts[i]);
+        out[missing[i]] = pts[i];
+    }
+    return out;
 }
 
 CtPtr DirectSortN::blindRotationOptN(const std::vector<CtPtr> &mi, int num_slots, int np, int ib, int num_partition) {

@@ -228,7 +228,8 @@ class DirectSortN {
     // (Engine::mul_columns); the masked sums, giant steps, lane partials, the
     // shard reduction and the fold then run on column stacks.  A column deeper
     // than the series output (indexSeriesLevel) is refused before any work.
-    // With tied keys the columns mix exactly as the key does (tests/tie_model.py).
+    // With tied keys the columns mix exactly as the key does (tests/tie_model.py)
+    // unless the rank was built with `tiebreak` set.
     std::vector<CtPtr> rotationIndexCheckColumns(const Ciphertext &rank, const std::vector<const Ciphertext *> &cols);
     // constructRank(key), then rotationIndexCheckColumns
     std::vector<CtPtr> sortColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols, SignFunc f,
@@ -248,8 +249,8 @@ class DirectSortN {
     // words do not depend on the chunking.  Same depth and output level as the
     // sort; a column deeper than the series output is refused before any work.
     // Unsharded.  With tied keys the result mixes as the sort does
-    // (tests/tie_model.py).  cache_masks false: the call re-encodes its own
-    // plaintexts at its start.
+    // (tests/tie_model.py) unless the rank was built with `tiebreak` set.
+    // cache_masks false: the call re-encodes its own plaintexts at its start.
     std::vector<CtPtr> selectColumns(const Ciphertext &rank, const std::vector<const Ciphertext *> &cols,
                                      const std::vector<int> &targets);
     // constructRank(key), then selectColumns
@@ -288,6 +289,14 @@ class DirectSortN {
     // 714-716); masks are encoded on the device either way (FHE_HOST_MASKS=1:
     // the host encoder, A/B)
     bool cache_masks = true;
+    // Tie-breaking for keys with equal values (0 = off, the
+    // reference's rank).  eps in (0, 0.5): constructRank adds a public offset of
+    // +-eps to every difference before the sign (Engine::sub_add_plain_stacked),
+    // so the rank is the stable argsort rank #{x_j < x_e} + #{j < e : x_j = x_e}.
+    // Needs distinct values >= 2 eps apart, a sign configuration that resolves
+    // eps, and |x_i - x_j| + eps <= 1.  No extra depth; the output level is
+    // unchanged.
+    double tiebreak = 0.0;
 
   private:
     struct Lane {
@@ -321,6 +330,9 @@ class DirectSortN {
     std::mutex mask_mu;
     // the select's {C, K} plaintexts per (targets of the member, member, level of C, level of K)
     std::map<std::tuple<std::vector<int>, int, int, int>, std::array<PtPtr, 2>> select_cache;
+    // the tie-break offsets E_b per (num_slots, batch, level, eps)
+    std::map<std::tuple<int, int, int, double>, PtPtr> tiebreak_cache;
+    std::map<int, PtPtr> tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level);
     std::vector<int> rot_indices;
     std::vector<std::unique_ptr<Engine>> lane_eng;
     std::vector<std::unique_ptr<RotationComposerN>> lane_rot;

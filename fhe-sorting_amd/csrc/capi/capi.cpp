@@ -33,6 +33,7 @@ struct fhe_ctx {
     int sort_lanes = 2;
     int sort_col_members = 256;  // fhe_set_sort_column_members (initial value: FHE_SORT_COLS_MEMBERS)
     bool mask_cache = true;  // fhe_set_mask_cache
+    double sort_tiebreak = 0.0;  // fhe_set_sort_tiebreak
     std::unique_ptr<Engine> kway_lane;  // the k-way sorter's second lane (forked on first use)
     bool kway_stack = false;            // fhe_set_kway_stack (initial value: FHE_KWAY_STACK)
 };
@@ -585,6 +586,7 @@ int fhe_direct_sort(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
         ds.max_stack = ctx->sort_stack;
         ds.lanes = ctx->sort_lanes;
         ds.cache_masks = ctx->mask_cache;
+        ds.tiebreak = ctx->sort_tiebreak;
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
         ds.allreduce = std::move(reduce);
@@ -627,6 +629,7 @@ int fhe_direct_sort_columns(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank,
         ds.lanes = ctx->sort_lanes;
         ds.max_col_members = ctx->sort_col_members;
         ds.cache_masks = ctx->mask_cache;
+        ds.tiebreak = ctx->sort_tiebreak;
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
         ds.allreduce = std::move(reduce);
@@ -697,6 +700,7 @@ int fhe_direct_select(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const
         ds.lanes = ctx->sort_lanes;
         ds.max_col_members = ctx->sort_col_members;
         ds.cache_masks = ctx->mask_cache;
+        ds.tiebreak = ctx->sort_tiebreak;
         ds.shard_rank = 0;  // selection is unsharded; a sharded caller passes the reduced rank in
         ds.shard_world = 1;
         ds.allreduce = nullptr;
@@ -770,6 +774,7 @@ int fhe_sort_hybrid(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
         ds.allreduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);
+        ds.tiebreak = ctx->sort_tiebreak;
         ds.hybrid_max_array = max_array;
         ds.hybrid_mask = mask_mode;
         if (mode == 1) {
@@ -1109,6 +1114,53 @@ int fhe_set_mask_cache(fhe_ctx *ctx, int cache) {
     });
 }
 
+int fhe_set_sort_tiebreak(fhe_ctx *ctx, double eps) {
+    return guard([&] {
+        NEED(ctx);
+        if (!(eps >= 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_set_sort_tiebreak: eps must lie in [0, 0.5)");
+        ctx->sort_tiebreak = eps;
+    });
+}
+int fhe_tiebreak_offsets(int N, int num_slots, int batch, double eps, double *out) {
+    return guard([&] {
+        NEED(out);
+        const std::vector<double> v = Engine::tiebreak_offsets(N, num_slots, batch, eps);
+        std::memcpy(out, v.data(), v.size() * sizeof(double));
+    });
+}
+int fhe_pt_encode_tiebreak(fhe_ctx *ctx, const int32_t *batches, int count, int num_slots, int N, double eps,
+                           int level, fhe_pt **out) {
+    if (out)
+        for (int i = 0; i < count; ++i) out[i] = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        NEED(batches);
+        NEED(out);
+        if (count < 1) throw std::invalid_argument("fhe_pt_encode_tiebreak: count must be >= 1");
+        auto pts = ctx->eng->encode_tiebreak(std::vector<int>(batches, batches + count), num_slots, N, eps, level);
+        for (int i = 0; i < count; ++i) out[i] = new fhe_pt{pts[(size_t)i]};
+    });
+}
+int fhe_sub_add_plain_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, const fhe_pt *const *ps,
+                              int count, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(bs);
+        NEED(ps);
+        NEED(out);
+        if (count < 1) throw std::invalid_argument("fhe_sub_add_plain_stacked: count must be >= 1");
+        std::vector<const Ciphertext *> b;
+        std::vector<const Plaintext *> p;
+        for (int i = 0; i < count; ++i) {
+            NEED(bs[i]);
+            NEED(ps[i]);
+            b.push_back(bs[i]->p.get());
+            p.push_back(ps[i]->p.get());
+        }
+        *out = wrap(ctx->eng->sub_add_plain_stacked(*a->p, b, p));
+    });
+}
 int fhe_set_sort_stack(fhe_ctx *ctx, int max_stack) {
     return guard([&] {
         NEED(ctx);

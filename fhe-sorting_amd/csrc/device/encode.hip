@@ -18,7 +18,8 @@
 // The sort's public masks are generated on the device too (kernel k_mask_slots:
 // mask_vector(k) rotated by r, checking_vector(k), src/sort_algo.h:206-233,
 // 272-286), so a batch of masks needs no host-to-device copy of slot values;
-// so are the target / pick vectors of the order-statistic select (k_select_slots).
+// so are the target / pick vectors of the order-statistic select (k_select_slots)
+// and the tie-break offsets of the rank's comparator batches (k_tiebreak_slots).
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -135,6 +136,21 @@ __global__ __launch_bounds__(256) void k_select_slots(double2 *vc, double2 *vk, 
     vk[i] = make_double2(in && r == 0 ? 1.0 : 0.0, 0.0);
 }
 
+// tie-break offsets of the rank's comparator batches: slot s of
+// batch b compares element e = s mod N with element (e + t) mod N, t = b S / N +
+// s / N; the offset is +eps where that element is e itself or comes before it
+// (t == 0 or e + t >= N), -eps where it comes after.  One thread per slot of
+// every member.
+__global__ __launch_bounds__(256) void k_tiebreak_slots(double2 *v, int S, int N, const int *batches, double eps,
+                                                        size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int m = (int)(i / S), s = (int)(i % S);
+    const long long t = (long long)batches[m] * (S / N) + s / N;
+    const bool before = t == 0 || (long long)(s % N) + t >= N;
+    v[i] = make_double2(before ? eps : -eps, 0.0);
+}
+
 }  // namespace
 
 void encode_ifft(double2 *v, int64_t *coef, int B, int S, int n, const double2 *ksi, const uint32_t *rot,
@@ -165,6 +181,13 @@ void select_slots(double2 *vc, double2 *vk, int S, int N, const int *targets, in
     if (S <= 0) return;
     launch_clocked("k_select_slots", 2.0 * S * sizeof(double2), k_select_slots, dim3((unsigned)((S + 255) / 256)),
                    dim3(256), st, vc, vk, S, N, targets, count, shift);
+}
+
+void tiebreak_slots(double2 *v, int B, int S, int N, const int *batches, double eps, hipStream_t st) {
+    const size_t total = (size_t)B * S;
+    if (!total) return;
+    launch_clocked("k_tiebreak_slots", (double)total * sizeof(double2), k_tiebreak_slots,
+                   dim3((unsigned)((total + 255) / 256)), dim3(256), st, v, S, N, batches, eps, total);
 }
 
 }  // namespace dev

@@ -1344,6 +1344,49 @@ __global__ __launch_bounds__(NT) void k_mul_plain_sum_groups(u64 *out, const u64
         }
 }
 
+// The tie-broken differences of a chunk of comparator batches (constructRank,
+// DESIGN.md §6.3): member i of out = (a - b_i) + p_i on c0, a - b_i on c1, written
+// straight into the stack.  a is one ciphertext, so a thread loads its two pairs
+// of words once and applies them to the SAP_TM members of its tile:
+// 5 B + 2 ceil(B / TM) limb-units against the 9 B of sub_stacked followed by an
+// add_plain per member.  sub_mod then add_mod, the words of k_sub and k_c0_op.
+// A last tile narrower than SAP_TM repeats its last member and stores only the
+// valid ones.  grid: x = coefficient block, y = limb, z = member tile.
+constexpr int SAP_TM = 4;
+struct SubAddPlainArgs {
+    const u64 *b[LIN_MAX];
+    const u64 *p[LIN_MAX];
+    int B;
+};
+__global__ __launch_bounds__(NT) void k_sub_add_plain_stacked(u64 *out, const u64 *a, SubAddPlainArgs A, size_t ln_all,
+                                                              const Mod *mods, int logN) {
+    constexpr int TM = SAP_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int m0 = blockIdx.z * TM;
+    const ulonglong2 a0 = ld2(a + lo), a1 = ld2(a + ln_all + lo);
+    ulonglong2 b0[TM], b1[TM], p[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const int m = min(m0 + t, A.B - 1);  // block-uniform
+        b0[t] = ld2(A.b[m] + lo);
+        b1[t] = ld2(A.b[m] + ln_all + lo);
+        p[t] = ld2(A.p[m] + lo);
+    }
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+        if (m0 + t < A.B) {
+            u64 *o = out + (size_t)(m0 + t) * 2 * ln_all + lo;
+            st2(o, make_ulonglong2(add_mod(sub_mod(a0.x, b0[t].x, q), p[t].x, q),
+                                   add_mod(sub_mod(a0.y, b0[t].y, q), p[t].y, q)));
+            st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
+        }
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3151,6 +3194,24 @@ void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int
         const double B = 8.0 * (2.0 * A.m * groups + (double)A.m * gtiles + 2.0 * groups * (1 + A.accumulate)) * ln_all;
         launch_clocked("k_mul_plain_sum_groups", B, k_mul_plain_sum_groups, ew_grid(logN, limbs, gtiles), dim3(NT), st,
                        out, in, A, ln_all, mods, logN);
+    }
+}
+int sub_add_plain_tile() { return SAP_TM; }
+void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, const u64 *const *ps, int members,
+                              int limbs, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < members; base += LIN_MAX) {
+        SubAddPlainArgs A{};
+        A.B = std::min(LIN_MAX, members - base);
+        for (int i = 0; i < A.B; ++i) {
+            A.b[i] = bs[base + i];
+            A.p[i] = ps[base + i];
+        }
+        const int tiles = (A.B + SAP_TM - 1) / SAP_TM;
+        const double B = 8.0 * (5.0 * A.B + 2.0 * tiles) * ln_all;
+        launch_clocked("k_sub_add_plain_stacked", B, k_sub_add_plain_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
+                       out + (size_t)base * 2 * ln_all, a, A, ln_all, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

@@ -258,6 +258,13 @@ void ew_mul_plain_sum_batches(u64 *out, const u64 *const *cts, const u64 *const 
 int plain_sum_groups_tile();
 void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int m, int groups, int limbs,
                              const Mod *mods, int logN, hipStream_t st);
+// Member i of out ([members][2][limbs][n]) = a - bs[i] with ps[i] added to c0
+// (a, bs[i]: [2][limbs][n], ps[i]: [limbs][n]), in one pass.  A thread applies
+// a's words to up to sub_add_plain_tile() members; word for word ew_sub, then
+// ew_c0_op mode 1, per member.
+int sub_add_plain_tile();
+void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, const u64 *const *ps, int members,
+                              int limbs, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);
@@ -289,6 +296,10 @@ void mask_slots(double2 *v, int B, int S, int N, const int *spec, hipStream_t st
 // targets[q] (device array) on window q, vk [S] holds 1 at each window's first
 // slot, both 0 elsewhere.  Needs count (N + 1) - 1 <= S.
 void select_slots(double2 *vc, double2 *vk, int S, int N, const int *targets, int count, int shift, hipStream_t st);
+// the tie-break offsets of constructRank's comparator batches:
+// member m of v [B][S] belongs to batch batches[m] (device array); slot s holds
+// +eps where (s mod N) + t >= N or t == 0, t = batch (S / N) + s / N, else -eps
+void tiebreak_slots(double2 *v, int B, int S, int N, const int *batches, double eps, hipStream_t st);
 
 // ---------------------------------------------------------------- keyswitch
 // ext[m][j][t][k] for every member m, digit j and target t not in digit j

@@ -1227,6 +1227,46 @@ std::array<PtPtr, 2> Engine::encode_select(const std::vector<int> &targets, int 
     return {sorted[ic], sorted[ik]};
 }
 
+std::vector<double> Engine::tiebreak_offsets(int N, int num_slots, int batch, double eps) {
+    select_cap(N, num_slots);  // validates the shape
+    const int parts = num_slots / N;
+    if (batch < 0 || (long long)batch * parts >= N)
+        throw std::invalid_argument("tiebreak offsets: batch " + std::to_string(batch) + " is outside [0, N / (num_slots / N))");
+    if (!(eps >= 0.0 && eps < 0.5)) throw std::invalid_argument("tiebreak offsets: eps must lie in [0, 0.5)");
+    std::vector<double> v((size_t)num_slots);
+    for (int s = 0; s < num_slots; ++s) {
+        const long long t = (long long)batch * parts + s / N;
+        v[(size_t)s] = (t == 0 || s % N + t >= N) ? eps : -eps;
+    }
+    return v;
+}
+
+std::vector<PtPtr> Engine::encode_tiebreak(const std::vector<int> &batches, int num_slots, int N, double eps, int level) {
+    auto &I = *impl;
+    const int B = (int)batches.size();
+    if (B == 0) return {};
+    select_cap(N, num_slots);  // validates the shape
+    const int parts = num_slots / N;
+    if ((size_t)num_slots > I.n() / 2) throw std::invalid_argument("encode_tiebreak: slots must be a power of two <= n/2");
+    if (!(eps >= 0.0 && eps < 0.5)) throw std::invalid_argument("encode_tiebreak: eps must lie in [0, 0.5)");
+    if (level < 0 || level > I.P.L) throw std::invalid_argument("encode_tiebreak: level out of range");
+    for (int b : batches)
+        if (b < 0 || (long long)b * parts >= N)
+            throw std::invalid_argument("encode_tiebreak: batch " + std::to_string(b) + " is outside [0, N / (num_slots / N))");
+    const u64 t0 = now_ns();
+    I.enc_tables();
+    const std::vector<int> levels((size_t)B, level);
+    const std::vector<double> scales((size_t)B, I.P.delta[level]);
+    auto vm = I.alloc((size_t)B * num_slots * sizeof(double2));
+    auto bm = I.alloc((size_t)B * 4);
+    HIP_OK(hipMemcpyAsync(bm->p, batches.data(), (size_t)B * 4, hipMemcpyHostToDevice, I.st));
+    dev::tiebreak_slots(static_cast<double2 *>(vm->p), B, num_slots, N, static_cast<const int *>(bm->p), eps, I.st);
+    auto out = I.encode_sorted(static_cast<double2 *>(vm->p), B, num_slots, levels, scales);  // synchronises: `batches` outlives its copy
+    host_stats().encode_ns += now_ns() - t0;
+    host_stats().encodes += B;
+    return out;
+}
+
 std::vector<PtPtr> Engine::encode_device(const std::vector<std::vector<double>> &vs, int slots,
                                          const std::vector<int> &levels) {
     auto &I = *impl;
@@ -2426,6 +2466,63 @@ CtPtr Engine::sub_stacked(const Ciphertext &a0, const std::vector<const Cipherte
     for (size_t i = 0; i < bs.size(); ++i)
         dev::ew_sub(r->data + i * 2 * ln, a->data, bs[i]->data, (int)a->limbs, 2, seg3(ln, ln, ln), MODS, LOGN, ST);
     count_bytes(6.0 * a->limbs, (int)bs.size());
+    return r;
+}
+// FHE_TIEBREAK_FUSED (A/B, default 1): sub_add_plain_stacked's one-pass kernel
+static bool tiebreak_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_TIEBREAK_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+CtPtr Engine::sub_add_plain_stacked(const Ciphertext &a0, const std::vector<const Ciphertext *> &bs,
+                                    const std::vector<const Plaintext *> &ps) {
+    if (bs.empty()) throw std::invalid_argument("sub_add_plain_stacked: no operands");
+    if (ps.size() != bs.size()) throw std::invalid_argument("sub_add_plain_stacked: one plaintext per operand");
+    if (a0.batch != 1) throw std::invalid_argument("sub_add_plain_stacked: a must be one ciphertext");
+    for (auto *b : bs)
+        if (!b || b->level != bs[0]->level || b->batch != 1)
+            throw std::invalid_argument("sub_add_plain_stacked: operands differ in level");
+    // the plaintexts meet the differences, which sit at the deeper of the two levels
+    const int level = std::max(a0.level, bs[0]->level);
+    for (auto *p : ps)
+        if (!p || p->level != level) throw std::invalid_argument("sub_add_plain_stacked: level mismatch");
+    if (a0.level > bs[0]->level) {  // every b is adjusted instead: per-member ops, as sub_stacked
+        std::vector<CtPtr> d;
+        std::vector<const Ciphertext *> v;
+        for (size_t i = 0; i < bs.size(); ++i) {
+            d.push_back(add_plain(*sub(a0, *bs[i]), *ps[i]));
+            v.push_back(d.back().get());
+        }
+        return stack(v);
+    }
+    const size_t nn = n();
+    if (!tiebreak_fused_enabled()) {  // the plain form (A/B): the stacked differences, then c0 += p_i in place
+        CtPtr r = sub_stacked(a0, bs);
+        const size_t ln = r->limbs * nn;
+        for (size_t i = 0; i < ps.size(); ++i) {
+            u64 *c0 = r->data + i * 2 * ln;
+            dev::ew_add(c0, c0, ps[i]->data, (int)r->limbs, 1, seg3(ln, ln, ln), MODS, LOGN, ST);
+        }
+        count_bytes(3.0 * r->limbs, (int)ps.size());
+        return r;
+    }
+    CtPtr a = std::make_shared<Ciphertext>(a0);
+    if (a->level < level) a = level_adjust(*a, level);  // sub(a, b) adjusts a the same way
+    const size_t ell = a->limbs;
+    const int B = (int)bs.size();
+    auto r = new_ct(a->level, a->slots, a->scale, ell, B);
+    std::vector<const u64 *> bp, pp;
+    for (int i = 0; i < B; ++i) {
+        if (bs[i]->limbs != ell || ps[i]->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_add_plain_stacked: operand limb count differs from its level's");
+        bp.push_back(bs[i]->data);
+        pp.push_back(ps[i]->data);
+    }
+    dev::ew_sub_add_plain_stacked(r->data, a->data, bp.data(), pp.data(), B, (int)ell, MODS, LOGN, ST);
+    const int tile = dev::sub_add_plain_tile();
+    count_bytes(5.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {

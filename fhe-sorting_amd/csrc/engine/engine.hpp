@@ -179,6 +179,16 @@ class Engine {
     // plaintext equals encode() of its vector word for word.
     std::array<PtPtr, 2> encode_select(const std::vector<int> &targets, int member, int num_slots, int N, int level_c,
                                        int level_k);
+    // Tie-break offsets of the rank's comparator batches (DirectSortN::constructRank,
+    // DESIGN.md §6.3).  Slot s of batch b compares element e = s mod N with element
+    // (e + t) mod N, t = b num_slots / N + s / N; the offset is +eps where that
+    // element is e itself or precedes it (t == 0 or e + t >= N), -eps elsewhere.
+    // tiebreak_offsets is the host definition; encode_tiebreak fills the vectors
+    // of a list of batches on the device (k_tiebreak_slots) and encodes them as
+    // one batch at `level`, each plaintext equal to encode() of its vector word
+    // for word.
+    static std::vector<double> tiebreak_offsets(int N, int num_slots, int batch, double eps);
+    std::vector<PtPtr> encode_tiebreak(const std::vector<int> &batches, int num_slots, int N, double eps, int level);
     // targets per member (cap) of that layout; throws unless N and num_slots / N
     // are powers of two with num_slots / N <= N
     static int select_cap(int N, int num_slots);
@@ -300,6 +310,14 @@ class Engine {
     // the bs' level once), and member i = a - ps[i]
     CtPtr sub_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs);
     CtPtr sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps);
+    // member i = add_plain(sub(a, bs[i]), ps[i]) word for word, written straight
+    // into the stack by one launch (k_sub_add_plain_stacked: a's words loaded once
+    // per tile of members).  sub_stacked's level rules: a at a lower level than
+    // the bs is level-adjusted once, a at a higher one takes per-member ops; the
+    // ps sit at the differences' level.  FHE_TIEBREAK_FUSED=0 (A/B): sub_stacked,
+    // then c0 += ps[i] per member.
+    CtPtr sub_add_plain_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs,
+                                const std::vector<const Plaintext *> &ps);
     CtPtr sum_members(const Ciphertext &a);
     // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
     // consecutive members, in one launch (k_sum_member_groups); an empty acc

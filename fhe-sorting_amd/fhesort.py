@@ -138,6 +138,12 @@ _SIGS = {
     'fhe_pt_encode_select': (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        PP]),
     'fhe_mul_plain_sum_groups': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_set_sort_tiebreak': (C.c_int, [vp, C.c_double]),
+    'fhe_tiebreak_offsets': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, dp]),
+    'fhe_pt_encode_tiebreak': (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                         C.POINTER(C.c_void_p)]),
+    'fhe_sub_add_plain_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
+                                            C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -769,7 +775,8 @@ class Context:
         rank=...) gives, word for word -- with the index series evaluated once for
         all columns.  rank=None: the rank is constructed from `key`; with a rank,
         key may be None.  Pass the key among cols to get it sorted too.  With tied
-        keys the columns mix exactly as the key does (tests/tie_model.py)."""
+        keys the columns mix exactly as the key does (tests/tie_model.py) unless
+        set_sort_tiebreak is set: then they come out in the stable permutation."""
         r = np.asarray(rots, dtype=np.int32)
         cols = list(cols)
         arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
@@ -792,7 +799,8 @@ class Context:
         (direct_sort mode 1), key may be None when cols are given.  Up to P_ - 1
         targets (num_slots = N * P_) cost one index series on one ciphertext.  With
         tied keys the result mixes values exactly as the sort does
-        (tests/tie_model.py): exact order statistics need distinct keys."""
+        (tests/tie_model.py) unless set_sort_tiebreak is set: then the order
+        statistics are exact."""
         r = np.asarray(rots, dtype=np.int32)
         t = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
         single = cols is None
@@ -821,6 +829,33 @@ class Context:
     @staticmethod
     def select_layout(N, num_slots, ntargets):
         return select_layout(N, num_slots, ntargets)
+
+    def set_sort_tiebreak(self, eps):
+        """Tie-breaking for keys with equal values (fhe_set_sort_tiebreak): with
+        0 < eps < 0.5 every rank built afterwards (direct_sort modes 0 and 1,
+        direct_sort_columns / direct_select without a rank, sort_hybrid) is the
+        stable argsort rank -- earlier index first among equals -- at the plain
+        sort's depth and output level.  Distinct values must differ by >= 2 eps,
+        the sign configuration must resolve eps, and |x_i - x_j| + eps <= 1.
+        0 (the default) is the reference's rank."""
+        _chk(lib().fhe_set_sort_tiebreak(self.h, float(eps)))
+
+    def encode_tiebreak(self, batches, num_slots, N, eps, level):
+        """fhe_pt_encode_tiebreak: the offsets of the given comparator batches,
+        filled and encoded on the device as one batch"""
+        b = np.ascontiguousarray(batches, dtype=np.int32).reshape(-1)
+        outs = (C.c_void_p * max(1, len(b)))()
+        _chk(lib().fhe_pt_encode_tiebreak(self.h, b.ctypes.data_as(C.POINTER(C.c_int32)), len(b), num_slots, N,
+                                          float(eps), level, outs))
+        return [Pt(self, outs[i]) for i in range(len(b))]
+
+    def sub_add_plain_stacked(self, a, bs, ps):
+        """stack whose member i is add_plain(sub(a, bs[i]), ps[i]) word for word, in one pass"""
+        ba = (C.c_void_p * max(1, len(bs)))(*[b.h for b in bs])
+        pa = (C.c_void_p * max(1, len(ps)))(*[p.h for p in ps])
+        if len(bs) != len(ps):
+            raise ValueError('sub_add_plain_stacked: one plaintext per operand')
+        return self._new(lib().fhe_sub_add_plain_stacked, a.h, ba, pa, len(bs))
 
     def mul_columns(self, a, cols):
         """the stack a (B members) times each single ciphertext of cols: member
@@ -1090,6 +1125,14 @@ def select_layout(N, num_slots, ntargets):
     if m < 0:
         raise FheError(-m, lib().fhe_last_error().decode())
     return m, [int(x) for x in member], [int(x) for x in start]
+
+
+def tiebreak_offsets(N, num_slots, batch, eps):
+    """fhe_tiebreak_offsets (pure host): the +-eps offsets of comparator batch
+    `batch` of a rank over num_slots slots"""
+    out = np.empty(max(int(num_slots), 0), dtype=np.float64)
+    _chk(lib().fhe_tiebreak_offsets(N, num_slots, batch, float(eps), _dbl(out)))
+    return out
 
 
 def mehp24_parameters(N):

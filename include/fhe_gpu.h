@@ -269,8 +269,10 @@ int fhe_direct_sort(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
  * rank, the key's), and for a missing key and rank; FHE_EDEPTH for a column below
  * the level of the series output (the product could not meet it there), raised
  * before the index check starts.  On failure no output handle is set.  With tied
- * keys the columns are mixed exactly as the key is (tests/tie_model.py): a true
- * permutation needs distinct keys. */
+ * keys the columns are mixed exactly as the key is (tests/tie_model.py) unless
+ * fhe_set_sort_tiebreak is set: then the rank built here is the stable one and
+ * the columns come out in the stable permutation.  A rank passed in is used as
+ * given. */
 int fhe_direct_sort_columns(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols,
                             int ncols, int N, const int32_t *rots, int nrot, int n, int dg, int df,
                             int shard_rank, int shard_world, fhe_allreduce_fn allreduce, void *user,
@@ -309,8 +311,10 @@ int fhe_ct_sum_member_groups(fhe_ctx *ctx, const fhe_ct *a, int groups, fhe_ct *
  * [0, N) (the message names the first such target's index); FHE_EDEPTH for a
  * column below the level of the series output.  On failure every output handle
  * is NULL.  With tied keys the result mixes values exactly as the sort does
- * (tests/tie_model.py): exact order statistics need distinct keys.  With
- * fhe_set_mask_cache(ctx, 0) a call re-encodes its own plaintexts at its start. */
+ * (tests/tie_model.py) unless fhe_set_sort_tiebreak is set: then the rank built
+ * here is the stable one and the order statistics are exact.  A rank passed in
+ * is used as given.  With fhe_set_mask_cache(ctx, 0) a call re-encodes its own
+ * plaintexts at its start. */
 int fhe_direct_select(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const fhe_ct *const *cols, int ncols,
                       const int32_t *targets, int ntargets, int N, const int32_t *rots, int nrot, int n, int dg,
                       int df, fhe_ct **outs /* ncols handles */);
@@ -335,6 +339,45 @@ int fhe_pt_encode_select(fhe_ctx *ctx, const int32_t *targets, int ntargets, int
  * (FHE_SELECT_FUSED=0: one fhe_mul_plain_sum per group, stacked). */
 int fhe_mul_plain_sum_groups(fhe_ctx *ctx, const fhe_ct *stack, const fhe_pt *const *pts, int npts, int groups,
                              fhe_ct **out);
+
+/* Tie-breaking for keys that contain equal values (the project's own extension;
+ * DESIGN.md §6.3).  The reference's rank gives a value of multiplicity m the rank
+ * #{smaller} + (m - 1) / 2, so tied inputs do not sort (tests/tie_model.py).  With
+ * eps > 0 every entry that builds a rank -- fhe_direct_sort modes 0 and 1,
+ * fhe_direct_sort_columns and fhe_direct_select with rank == NULL, fhe_sort_hybrid
+ * mode 0 -- adds a public offset to each difference x_e - x_j before the sign:
+ * +eps where j <= e (the self comparison included), -eps where j > e.  The rank
+ * is then the stable argsort rank #{x_j < x_e} + #{j < e : x_j = x_e}: among equal
+ * values the earlier index comes first.  The offset is a plaintext addition:
+ * levels, depth, keys and the output level are the plain sort's, and no sign is
+ * evaluated at 0.  The caller guarantees that
+ *   - distinct values differ by at least 2 eps,
+ *   - the sign configuration (n, dg, df) resolves eps: sign(+-eps) = +-1 to the
+ *     precision the index check needs,
+ *   - |x_i - x_j| + eps <= 1, the sign's domain.
+ * eps = 0 (the default) is the reference's rank, word for word as before.
+ * 0 <= eps < 0.5, else FHE_EINVAL.  A rank passed in (mode 2, rank != NULL) is
+ * used as given.  The offset plaintexts are cached per context like the masks
+ * (fhe_set_mask_cache(ctx, 0): re-encoded at the start of every rank). */
+int fhe_set_sort_tiebreak(fhe_ctx *ctx, double eps);
+/* pure host: the offsets of comparator batch `batch` over num_slots = N P_ slots
+ * (N and P_ powers of two, P_ <= N, 0 <= batch < N / P_).  Slot s compares element
+ * e = s mod N with element (e + t) mod N, t = batch P_ + s / N; out[s] = +eps where
+ * e + t >= N or t == 0, -eps elsewhere.  Writes num_slots doubles. */
+int fhe_tiebreak_offsets(int N, int num_slots, int batch, double eps, double *out);
+/* for tests and bindings: those vectors of `count` batches, filled and encoded on
+ * the device as one batch at `level`; each equals fhe_pt_encode of its vector
+ * word for word. */
+int fhe_pt_encode_tiebreak(fhe_ctx *ctx, const int32_t *batches, int count, int num_slots, int N, double eps,
+                           int level, fhe_pt **out /* count handles */);
+/* and the differences they enter: member i of the result is fhe_add_plain(fhe_sub(a,
+ * bs[i]), ps[i]) word for word, written into the stack by one kernel that loads a
+ * once per four members (FHE_TIEBREAK_FUSED=0, read once per process: the
+ * stacked differences, then one c0 addition per member).  The bs share a level;
+ * a at a lower level is level-adjusted once, a at a higher one takes per-member
+ * operations; the ps sit at the differences' level, else FHE_EINVAL. */
+int fhe_sub_add_plain_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, const fhe_pt *const *ps,
+                              int count, fhe_ct **out);
 
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
