@@ -1842,6 +1842,157 @@ std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &key, const std::
     return selectColumns(*rank, cols, targets);
 }
 
+GroupSumLevels groupSumLevels(int key_level, int n, int dg, int df, int ps_split) {
+    if (key_level < 0) throw std::invalid_argument("group sum: negative key level");
+    if (n != 3 && n != 4) throw std::invalid_argument("group sum: the composite sign's n must be 3 or 4");
+    if (dg < 0 || df < 0) throw std::invalid_argument("group sum: negative sign degrees");
+    const int g_depth = n == 3 ? 3 : chebPSDepthSplit((int)g4_coeffs().size() - 1, ps_split), f_depth = n;
+    GroupSumLevels lv;
+    lv.sign_depth = std::max(dg, 1) * g_depth + df * f_depth;
+    lv.diff_level = key_level + 1;
+    lv.match_level = lv.diff_level + lv.sign_depth;
+    lv.col_max_level = lv.match_level - 2;
+    lv.out_level = lv.match_level + 1;
+    return lv;
+}
+
+// Group sums and lookups.  Every (left row e, right row j) pair is met once, in
+// constructRank's layout: slot s of batch b holds kl[s mod N] - kr[(s mod N + t) mod N],
+// t = b P_ + s / N.  The same vecRotsOpt shift applied to a column puts
+// col[(s mod N + t) mod N] beside it, so indicator x column, summed over batches
+// and folded over the P_ partitions, is the sum over j.  The 1/2 that turns
+// sign(d + eps) + sign(-d + eps) (2 on a match) into the indicator rides on the
+// columns' level adjustment (mul_const_to 0.5), so the count alone pays it as a
+// closing mul_const.
+std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext &kr,
+                                          const std::vector<const Ciphertext *> &cols, double eps, bool want_count,
+                                          SignFunc f, const SignConfig &cfg) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)cols.size();
+    if (P == 0 && !want_count) throw std::invalid_argument("group sum: neither a column nor the count is asked for");
+    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("group sum: eps must lie in (0, 0.5)");
+    if (kl.batch != 1 || kr.batch != 1) throw std::invalid_argument("group sum: a key is a stack");
+    if (kl.slots != kr.slots) throw std::invalid_argument("group sum: the keys differ in slot count");
+    if (kl.level != kr.level)
+        throw std::invalid_argument("group sum: the keys sit at different levels (" + std::to_string(kl.level) + ", " +
+                                    std::to_string(kr.level) + ")");
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("group sum: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument("group sum: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->slots != kl.slots)
+            throw std::invalid_argument("group sum: column " + std::to_string(p) + " has " +
+                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(kl.slots));
+    }
+    const GroupSumLevels lv =
+        groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
+    if (lv.out_level > cc.params().L)
+        throw std::runtime_error("group sum: keys at level " + std::to_string(kl.level) + " need " +
+                                 std::to_string(lv.out_level) + " levels, the context has " +
+                                 std::to_string(cc.params().L) + ": no levels left");
+    for (int p = 0; p < P; ++p)
+        if (cols[p]->level > lv.col_max_level)
+            throw std::runtime_error("group sum: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
+                                     std::to_string(lv.col_max_level) + "): no levels left to meet the match indicator");
+    if (!cache_masks) refresh_masks();
+    std::optional<AlgoPhase> ph;
+    ph.emplace("group_baby");
+    std::vector<CtPtr> kbaby = babySteps(kr, s.np);
+    for (auto &b : kbaby) b->slots = s.num_slots;
+    // the columns, prepared once: halved on the way to one level above the match
+    // indicator's, then the baby steps every batch's shifted copy starts from
+    std::vector<std::vector<CtPtr>> cbaby(P);
+    for (int p = 0; p < P; ++p) {
+        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 0.5, lv.match_level - 1), s.np);
+        for (auto &b : cbaby[p]) b->slots = s.num_slots;
+    }
+    ph.reset();
+    std::vector<int> mine(s.num_batch);
+    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
+    CtPtr dup = cc.clone(kl);
+    dup->slots = s.num_slots;
+    cc.sync();  // the baby steps and dup are read by every lane
+    const size_t chunk = (size_t)std::max(1, max_stack);
+    // columns per stacked product, as rotationIndexCheckColumns bounds them
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
+    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
+    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level match_level)
+    std::mutex cnt_mu;
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph("group_batches");
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        CtPtr cnt;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr sg;
+            {
+                std::vector<CtPtr> shifted = vecRotsOptMany(L, kbaby, s.num_partition, s.num_slots, s.np, iss);
+                std::vector<const Ciphertext *> ptrs;
+                for (auto &x : shifted) ptrs.push_back(x.get());
+                // d_b + eps (members 0 .. B - 1) and -d_b + eps (members B .. 2 B - 1) of every batch
+                CtPtr d = E.sub_pm_const_stacked(*dup, ptrs, eps);
+                shifted.clear();
+                sg = sign(*d, E, f, cfg);
+            }
+            if (sg->level != lv.match_level) throw std::logic_error("group sum: unexpected sign output level");
+            Ciphertext up = *sg, dn = *sg;  // views of the two halves
+            up.batch = dn.batch = B;
+            dn.data = sg->data + (size_t)B * 2 * sg->limbs * E.n();
+            if (want_count) {
+                CtPtr m = E.add(up, dn);
+                E.add_inplace(cnt, B == 1 ? *m : *E.sum_members(*m));
+            }
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
+                for (int p = p0; p < p0 + Pg; ++p)
+                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
+                CtPtr prod = E.mul_pairs(up, dn, *asStack(E, sv), Pg);
+                sv.clear();
+                E.sum_member_groups(*prod, Pg, accs[g]);
+            }
+        }
+        if (cnt) {
+            std::lock_guard<std::mutex> lk(cnt_mu);
+            cnt_parts.push_back(cnt);
+        }
+        if (bs.empty() || P == 0) return nullptr;
+        if (accs.size() == 1) return accs[0];
+        std::vector<const Ciphertext *> all;
+        for (auto &a : accs) all.push_back(a.get());
+        return E.stack(all);  // the column groups, in column order
+    });
+    CtPtr out, cnt;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(out, *p);
+    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    cnt_parts.clear();
+    AlgoPhase fold_ph("group_fold");
+    auto fold = [&](CtPtr &v) {
+        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    };
+    std::vector<CtPtr> outs;
+    if (P > 0) {
+        fold(out);
+        for (int p = 0; p < P; ++p) {
+            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
+            outs.back()->slots = N;
+        }
+    }
+    if (want_count) {
+        fold(cnt);
+        outs.push_back(cc.mul_const(*cnt, 0.5));
+        outs.back()->slots = N;
+    }
+    return outs;
+}
+
 // Re-encodes every cached mask (the reference's per-use encoding,
 // src/sort_algo.h:341-342, 714-716) for sort() with mask caching off.  Chunks
 // of REFRESH_CHUNK masks: each chunk's new plaintexts replace (and release) old

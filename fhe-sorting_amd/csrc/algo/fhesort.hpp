@@ -185,6 +185,19 @@ SortShape checkShape(int N, int max_batch);
 // residue mod N once.  Returns the member count ceil(k / cap); member / start
 // (optional) receive k entries.  Throws std::invalid_argument on a bad shape.
 int selectLayout(int N, int num_slots, int k, std::vector<int> *member, std::vector<int> *start);
+// Levels of DirectSortN::groupSums for keys at key_level under the composite sign
+// (n, dg, df): sign_depth levels for the sign (3 per g_3 / f_3, 4 per f_4, g_4's
+// series depth under `ps_split`; g runs once even when dg = 0), the differences
+// at diff_level = key_level + 1 (one masked sum below the keys), the match
+// indicator at match_level = diff_level + sign_depth, the columns brought to
+// match_level - 1 before their own masked sum, so a column may sit at
+// col_max_level = match_level - 2 at most, and every output at
+// out_level = match_level + 1: where constructRank ends.  Throws
+// std::invalid_argument on a negative level or a sign the GPU path lacks.
+struct GroupSumLevels {
+    int sign_depth, diff_level, match_level, col_max_level, out_level;
+};
+GroupSumLevels groupSumLevels(int key_level, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
 
 // Sums a ciphertext's u64 limbs over ranks in place (device pointer, count
 // u64); the engine reduces mod q afterwards.  nullptr = single rank.
@@ -256,6 +269,26 @@ class DirectSortN {
     // constructRank(key), then selectColumns
     std::vector<CtPtr> selectColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
                                      const std::vector<int> &targets, SignFunc f, const SignConfig &cfg);
+    // Group sums and lookups (the project's own extension): with
+    // P = cols.size(), out[p] holds at slot e  sum_j [|kl_e - kr_j| < eps] cols[p]_j,
+    // j over the N rows of the right table; want_count appends the count of
+    // matching rows as out[P].  kr = kl is SUM / COUNT OVER (PARTITION BY key), the
+    // row itself included; another table's key and columns give the LEFT JOIN
+    // lookup, zero where no right key matches.  constructRank's all-pairs layout
+    // with the shifted right key and the same shifted copies of the columns
+    // (vecRotsOpt); the match indicator sign(d + eps) + sign(-d + eps) (2 or 0) of a
+    // chunk of B batches is one sign over a 2 B stack (Engine::sub_pm_const_stacked)
+    // and meets the columns, halved on their way to its level, in one stacked
+    // product (Engine::mul_pairs); sums over batches are exact mod q, then the
+    // rank's fold.  Needs equal keys equal up to noise far below eps, distinct keys
+    // >= 2 eps apart, |kl_e - kr_j| + eps <= 1 and a sign configuration that
+    // resolves eps (the tie-break's conditions).  Levels: groupSumLevels; a column
+    // above col_max_level or a context without out_level levels is refused before
+    // any work.  The words do not depend on max_stack, lanes, max_col_members or
+    // cache_masks (false: the call re-encodes the cached masks at its start).
+    // Unsharded; `tiebreak` has no effect.
+    std::vector<CtPtr> groupSums(const Ciphertext &kl, const Ciphertext &kr, const std::vector<const Ciphertext *> &cols,
+                                 double eps, bool want_count, SignFunc f, const SignConfig &cfg);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;

@@ -724,6 +724,93 @@ int fhe_select_layout(int N, int num_slots, int ntargets, int32_t *member, int32
     });
     return rc == FHE_OK ? count : -rc;
 }
+int fhe_direct_group_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *right_key, const fhe_ct *const *cols,
+                         int ncols, double eps, int N, const int32_t *rots, int nrot, int n, int dg, int df,
+                         fhe_ct **outs, fhe_ct **count_out) {
+    if (outs)
+        for (int p = 0; p < ncols; ++p) outs[p] = nullptr;
+    if (count_out) *count_out = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        if (!left_key || !left_key->p) throw std::invalid_argument("fhe_direct_group_sum: the left key is null");
+        if (!right_key || !right_key->p) throw std::invalid_argument("fhe_direct_group_sum: the right key is null");
+        if (ncols < 0) throw std::invalid_argument("fhe_direct_group_sum: ncols must be >= 0");
+        if (ncols == 0 && !count_out)
+            throw std::invalid_argument("fhe_direct_group_sum: neither a column nor the count is asked for");
+        if (ncols > 0 && (!cols || !outs)) throw std::invalid_argument("fhe_direct_group_sum: null column or output array");
+        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_group_sum: eps must lie in (0, 0.5)");
+        const Ciphertext &kl = *left_key->p, &kr = *right_key->p;
+        if (kl.batch != 1) throw std::invalid_argument("fhe_direct_group_sum: the left key is a stack");
+        if (kr.batch != 1) throw std::invalid_argument("fhe_direct_group_sum: the right key is a stack");
+        if (kr.slots != kl.slots)
+            throw std::invalid_argument("fhe_direct_group_sum: the right key has " + std::to_string(kr.slots) +
+                                        " slots, the left key " + std::to_string(kl.slots));
+        if (kr.level != kl.level)
+            throw std::invalid_argument("fhe_direct_group_sum: the keys sit at different levels (" +
+                                        std::to_string(kl.level) + ", " + std::to_string(kr.level) + ")");
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            const std::string which = "fhe_direct_group_sum: column " + std::to_string(p);
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
+            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (cols[p]->p->slots != kl.slots)
+                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the keys " +
+                                            std::to_string(kl.slots));
+            v.push_back(cols[p]->p.get());
+        }
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = 0;  // unsharded, like the select
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        // the depth refusals (a column too deep, a context too shallow) are raised
+        // by the operator before it starts any work
+        std::vector<CtPtr> r =
+            ds.groupSums(kl, kr, v, eps, count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
+        if (count_out) *count_out = wrap(r[(size_t)ncols]);
+    });
+}
+int fhe_group_sum_levels(int key_level, int n, int dg, int df, int *col_max_level, int *out_level) {
+    return guard([&] {
+        const GroupSumLevels lv = groupSumLevels(key_level, n, dg, df);
+        if (col_max_level) *col_max_level = lv.col_max_level;
+        if (out_level) *out_level = lv.out_level;
+    });
+}
+int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, int count, double c,
+                             fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(bs);
+        NEED(out);
+        if (count < 1) throw std::invalid_argument("fhe_sub_pm_const_stacked: count must be >= 1");
+        std::vector<const Ciphertext *> b;
+        for (int i = 0; i < count; ++i) {
+            NEED(bs[i]);
+            b.push_back(bs[i]->p.get());
+        }
+        *out = wrap(ctx->eng->sub_pm_const_stacked(*a->p, b, c));
+    });
+}
+int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_ct *b_stack, int ncols,
+                  fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(a_add);
+        NEED(b_stack);
+        NEED(out_stack);
+        *out_stack = wrap(ctx->eng->mul_pairs(*a->p, *a_add->p, *b_stack->p, ncols));
+    });
+}
 int fhe_pt_encode_select(fhe_ctx *ctx, const int32_t *targets, int ntargets, int member, int num_slots, int N,
                          int level_c, int level_k, fhe_pt **out) {
     if (out) out[0] = out[1] = nullptr;

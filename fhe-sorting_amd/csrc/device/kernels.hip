@@ -1387,6 +1387,105 @@ __global__ __launch_bounds__(NT) void k_sub_add_plain_stacked(u64 *out, const u6
         }
 }
 
+// The two-sided differences of a chunk of comparator batches (groupSums,
+// DESIGN.md §6.4): with d_i = a - b_i, member i of out = d_i + c on c0, d_i on c1,
+// and member `pm` + i = -d_i + c on c0, -d_i on c1, both written straight into
+// the stack from one load of b_i; a's two pairs of words are loaded once per tile
+// of SPM_TM members: 6 B + 2 ceil(B / TM) limb-units against the 18 B of
+// sub_stacked, negate and two add_consts.  sub_mod, sub_mod(0, .) and add_mod of
+// the constant's residue: the words of k_sub, k_neg and k_c0_op (mode 0).  A last
+// tile narrower than SPM_TM repeats its last member and stores only the valid
+// ones.  grid: x = coefficient block, y = limb, z = member tile.
+constexpr int SPM_TM = 4;
+struct SubPmConstArgs {
+    const u64 *b[LIN_MAX];
+    int B;
+};
+__global__ __launch_bounds__(NT) void k_sub_pm_const_stacked(u64 *out, const u64 *a, SubPmConstArgs A, size_t pm,
+                                                             int64_t K, int sh, size_t ln_all, const Mod *mods,
+                                                             int logN) {
+    constexpr int TM = SPM_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int m0 = blockIdx.z * TM;
+    const ulonglong2 a0 = ld2(a + lo), a1 = ld2(a + ln_all + lo);
+    ulonglong2 b0[TM], b1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const int m = min(m0 + t, A.B - 1);  // block-uniform
+        b0[t] = ld2(A.b[m] + lo);
+        b1[t] = ld2(A.b[m] + ln_all + lo);
+    }
+    const u64 w = smod(K, sh, mods[l]);
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+        if (m0 + t < A.B) {
+            const u64 d0x = sub_mod(a0.x, b0[t].x, q), d0y = sub_mod(a0.y, b0[t].y, q);
+            const u64 d1x = sub_mod(a1.x, b1[t].x, q), d1y = sub_mod(a1.y, b1[t].y, q);
+            u64 *o = out + (size_t)(m0 + t) * 2 * ln_all + lo;
+            st2(o, make_ulonglong2(add_mod(d0x, w, q), add_mod(d0y, w, q)));
+            st2(o + ln_all, make_ulonglong2(d1x, d1y));
+            u64 *om = o + pm * 2 * ln_all;
+            st2(om, make_ulonglong2(add_mod(sub_mod(0, d0x, q), w, q), add_mod(sub_mod(0, d0y, q), w, q)));
+            st2(om + ln_all, make_ulonglong2(sub_mod(0, d1x, q), sub_mod(0, d1y, q)));
+        }
+}
+
+// k_tensor with its a2 operand, of the stacks a and a2 (members at stride sa)
+// against a column-major stack b of P * members members (groupSums' match
+// indicator against the shifted columns): grid z = group *
+// members + z; a thread forms member z's a + a2 once (k_tensor's add_mod on
+// load) and the tensor against the up to PC columns of its group, member
+// p * members + z of b, every column's loads issued ahead of the arithmetic.
+// Output member p * members + z, the words k_tensor gives on (a[z], a2[z],
+// b[p * members + z]).  The last group is guarded.
+template <int PC>
+__global__ __launch_bounds__(NT) void k_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b,
+                                                     size_t ln_all, size_t sa, int P, int members, const Mod *mods,
+                                                     int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod m = mods[l];
+    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
+    const size_t o = (size_t)l * n + k;
+    const u64 *A = a + (size_t)z * sa, *A2 = a2 + (size_t)z * sa;
+    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
+    const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
+    ulonglong2 b0[PC], b1[PC];
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < P) {
+            const u64 *Bp = b + ((size_t)(p0 + j) * members + z) * 2 * ln_all;
+            b0[j] = ld2(Bp + o);
+            b1[j] = ld2(Bp + ln_all + o);
+        }
+    }
+    a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
+    a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < P) {
+            ulonglong2 e0, e1, e2;
+            e0.x = mul_barrett(a0.x, b0[j].x, m);
+            e0.y = mul_barrett(a0.y, b0[j].y, m);
+            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
+            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
+            e2.x = mul_barrett(a1.x, b1[j].x, m);
+            e2.y = mul_barrett(a1.y, b1[j].y, m);
+            const size_t mo = (size_t)(p0 + j) * members + z;
+            st2(d01 + mo * 2 * ln_all + o, e0);
+            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
+            st2(d2 + mo * ln_all + o, e2);
+        }
+    }
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3212,6 +3311,37 @@ void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, cons
         const double B = 8.0 * (5.0 * A.B + 2.0 * tiles) * ln_all;
         launch_clocked("k_sub_add_plain_stacked", B, k_sub_add_plain_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
                        out + (size_t)base * 2 * ln_all, a, A, ln_all, mods, logN);
+    }
+}
+int sub_pm_const_tile() { return SPM_TM; }
+void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, int64_t K, int sh, int limbs,
+                             const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < members; base += LIN_MAX) {
+        SubPmConstArgs A{};
+        A.B = std::min(LIN_MAX, members - base);
+        for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
+        const int tiles = (A.B + SPM_TM - 1) / SPM_TM;
+        const double B = 8.0 * (6.0 * A.B + 2.0 * tiles) * ln_all;
+        launch_clocked("k_sub_pm_const_stacked", B, k_sub_pm_const_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
+                       out + (size_t)base * 2 * ln_all, a, A, (size_t)members, K, sh, ln_all, mods, logN);
+    }
+}
+int tensor_pairs_per_thread() { return TC_PC; }
+void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
+                     size_t sa, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0 || P <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    // grid z = members * groups stays below the 65535 limit: whole column groups per launch
+    const int per_launch = std::max(1, 65535 / members / TC_PC) * TC_PC;
+    for (int base = 0; base < P; base += per_launch) {
+        const int Pn = std::min(per_launch, P - base), groups = (Pn + TC_PC - 1) / TC_PC;
+        const double B = 8.0 * (4.0 * members * groups + 5.0 * Pn * members) * ln_all;
+        const size_t mo = (size_t)base * members;  // first column member of this launch
+        launch_clocked(inst_name<TC_PC>("k_tensor_pairs"), B, k_tensor_pairs<TC_PC>, ew_grid(logN, limbs, members * groups),
+                       dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, a2, b + mo * 2 * ln_all, ln_all, sa, Pn,
+                       members, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

@@ -265,6 +265,22 @@ void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int
 int sub_add_plain_tile();
 void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, const u64 *const *ps, int members,
                               int limbs, const Mod *mods, int logN, hipStream_t st);
+// With d_i = a - bs[i]: member i of out ([2 members][2][limbs][n]) = d_i with
+// K 2^sh added to c0, member members + i = -d_i with K 2^sh added to c0, in one
+// pass (a, bs[i]: [2][limbs][n]).  A thread applies a's words to up to
+// sub_pm_const_tile() members; word for word ew_sub, then ew_c0_op mode 0, and
+// ew_neg, then ew_c0_op mode 0, per member.
+int sub_pm_const_tile();
+void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, int64_t K, int sh, int limbs,
+                             const Mod *mods, int logN, hipStream_t st);
+// ew_tensor with a2 of the stacks a, a2 (`members` members at stride sa) against
+// the column-major stack b of P * members members ([2][limbs][n] each) in one
+// pass: member p * members + z of d01 / d2 holds the tensor of (a[z] + a2[z],
+// b[p * members + z]), word for word ew_tensor's.  a + a2 is formed once per
+// tensor_pairs_per_thread() columns.
+int tensor_pairs_per_thread();
+void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
+                     size_t sa, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);

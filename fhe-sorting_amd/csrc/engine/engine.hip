@@ -1976,6 +1976,58 @@ CtPtr Engine::mul_columns(const Ciphertext &a, const std::vector<const Ciphertex
     return r;
 }
 
+// FHE_GROUP_FUSED (A/B, default 1): the one-pass kernels of mul_pairs and sub_pm_const_stacked
+static bool group_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_GROUP_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+
+CtPtr Engine::mul_pairs(const Ciphertext &a, const Ciphertext &a_add, const Ciphertext &b, int Pn) {
+    auto &I = *impl;
+    if (Pn < 1) throw std::invalid_argument("mul_pairs: no columns");
+    if (a.batch < 1 || a_add.batch != a.batch)
+        throw std::invalid_argument("mul_pairs: a and a_add differ in member count");
+    if (a_add.level != a.level || a_add.limbs != a.limbs)
+        throw std::invalid_argument("mul_pairs: a and a_add differ in level");
+    if ((long long)b.batch != (long long)Pn * a.batch)
+        throw std::invalid_argument("mul_pairs: b holds " + std::to_string(b.batch) + " members, need " +
+                                    std::to_string(Pn) + " columns of " + std::to_string(a.batch));
+    if (b.level != a.level || b.limbs != a.limbs) throw std::invalid_argument("mul_pairs: b is not at a's level");
+    const int B = a.batch, PB = Pn * B;
+    const size_t nn = n(), ell = a.limbs;
+    if (!group_fused_enabled()) {  // the plain form (A/B): one mul_add with a_add per column, stacked
+        std::vector<CtPtr> prod;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < Pn; ++p) {
+            Ciphertext col = b;
+            col.data = b.data + (size_t)p * B * 2 * ell * nn;
+            col.batch = B;
+            prod.push_back(mul_add(a, col, {}, {}, nullptr, &a_add));
+            v.push_back(prod.back().get());
+        }
+        return prod.size() == 1 ? prod[0] : stack(v);
+    }
+    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    ctr.hmult += PB;
+    ctr.keyswitch += PB;
+    ctr.rescale += PB;
+    count_bytes(5.0 * ell + ks_units(ell), PB);
+    const int per = dev::tensor_pairs_per_thread();
+    count_bytes(4.0 * ell * ((Pn + per - 1) / per), B);
+    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    dev::ew_tensor_pairs(d01, d2, a.data, a_add.data, b.data, Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    const bool fuse = I.ks_fuse(PB);
+    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
+    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
+    return r;
+}
+
 std::vector<CtPtr> Engine::rotate_hoisted(const Ciphertext &a, const std::vector<long> &ks) {
     auto &I = *impl;
     std::vector<u64> gs;
@@ -2523,6 +2575,45 @@ CtPtr Engine::sub_add_plain_stacked(const Ciphertext &a0, const std::vector<cons
     dev::ew_sub_add_plain_stacked(r->data, a->data, bp.data(), pp.data(), B, (int)ell, MODS, LOGN, ST);
     const int tile = dev::sub_add_plain_tile();
     count_bytes(5.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
+    return r;
+}
+CtPtr Engine::sub_pm_const_stacked(const Ciphertext &a0, const std::vector<const Ciphertext *> &bs, double c) {
+    if (bs.empty()) throw std::invalid_argument("sub_pm_const_stacked: no operands");
+    if (a0.batch != 1) throw std::invalid_argument("sub_pm_const_stacked: a must be one ciphertext");
+    for (auto *b : bs)
+        if (!b || b->level != bs[0]->level || b->batch != 1)
+            throw std::invalid_argument("sub_pm_const_stacked: operands differ in level");
+    const int B = (int)bs.size();
+    if (a0.level > bs[0]->level) {  // every b is adjusted instead: per-member ops, as sub_stacked
+        std::vector<CtPtr> d(2 * (size_t)B);
+        std::vector<const Ciphertext *> v;
+        for (int i = 0; i < B; ++i) {
+            CtPtr di = sub(a0, *bs[i]);
+            d[i] = add_const(*di, c);
+            d[B + i] = add_const(*negate(*di), c);
+        }
+        for (auto &x : d) v.push_back(x.get());
+        return stack(v);
+    }
+    if (!group_fused_enabled()) {  // the plain form (A/B): the stacked differences, then the two sides on the stack
+        CtPtr d = sub_stacked(a0, bs);
+        CtPtr plus = add_const(*d, c), minus = add_const(*negate(*d), c);
+        return stack({plus.get(), minus.get()});
+    }
+    CtPtr a = std::make_shared<Ciphertext>(a0);
+    if (a->level < bs[0]->level) a = level_adjust(*a, bs[0]->level);  // sub(a, b) adjusts a the same way
+    const size_t ell = a->limbs;
+    auto r = new_ct(a->level, a->slots, a->scale, ell, 2 * B);
+    std::vector<const u64 *> bp;
+    for (auto *b : bs) {
+        if (b->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_pm_const_stacked: operand limb count differs from its level's");
+        bp.push_back(b->data);
+    }
+    const host::SConst K = host::const_at_scale(c, a->scale);
+    dev::ew_sub_pm_const_stacked(r->data, a->data, bp.data(), B, K.k, K.sh, (int)ell, MODS, LOGN, ST);
+    const int tile = dev::sub_pm_const_tile();
+    count_bytes(6.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {

@@ -263,6 +263,13 @@ class Engine {
     // would not share a level).  FHE_SORT_COLS_FUSED=0
     // (A/B): P broadcast mul calls, stacked.
     CtPtr mul_columns(const Ciphertext &a, const std::vector<const Ciphertext *> &cols);
+    // the B-member stacks a and a_add against the column-major stack b of P B
+    // members, all at one level: member p B + z of the result is
+    // mul(add(member(a, z), member(a_add, z)), member(b, p B + z)) word for word.
+    // One tensor pass (k_tensor_pairs: a + a_add formed once per thread for up to
+    // four columns), then mul's relinearisation / rescale tail on P B members.
+    // FHE_GROUP_FUSED=0 (A/B): P mul_add(a, column p of b, a_add) calls, stacked.
+    CtPtr mul_pairs(const Ciphertext &a, const Ciphertext &a_add, const Ciphertext &b, int P);
     CtPtr square(const Ciphertext &a);
     CtPtr rotate(const Ciphertext &a, long k);
     std::vector<CtPtr> rotate_hoisted(const Ciphertext &a, const std::vector<long> &ks);
@@ -318,6 +325,14 @@ class Engine {
     // then c0 += ps[i] per member.
     CtPtr sub_add_plain_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs,
                                 const std::vector<const Plaintext *> &ps);
+    // with B = bs.size(): member i = add_const(sub(a, bs[i]), c) and member B + i =
+    // add_const(negate(sub(a, bs[i])), c) word for word, written straight into the
+    // 2 B stack by one launch (k_sub_pm_const_stacked: each bs[i] loaded once for
+    // both members, a's words once per tile of members).  The constant enters c0
+    // with add_const's residues at the differences' scale.  sub_stacked's level
+    // rules.  FHE_GROUP_FUSED=0 (A/B): sub_stacked, then negate / add_const on
+    // the stack, stacked.
+    CtPtr sub_pm_const_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs, double c);
     CtPtr sum_members(const Ciphertext &a);
     // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
     // consecutive members, in one launch (k_sum_member_groups); an empty acc

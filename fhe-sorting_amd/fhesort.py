@@ -144,6 +144,12 @@ _SIGS = {
                                          C.POINTER(C.c_void_p)]),
     'fhe_sub_add_plain_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
                                             C.POINTER(C.c_void_p)]),
+    'fhe_direct_group_sum': (C.c_int, [vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_double, C.c_int, ip, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    'fhe_group_sum_levels': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]),
+    'fhe_sub_pm_const_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_double,
+                                           C.POINTER(C.c_void_p)]),
+    'fhe_mul_pairs': (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -857,6 +863,44 @@ class Context:
             raise ValueError('sub_add_plain_stacked: one plaintext per operand')
         return self._new(lib().fhe_sub_add_plain_stacked, a.h, ba, pa, len(bs))
 
+    def group_sum(self, left_key, right_key, cols, eps, N, rots, cfg, count=False):
+        """Group sums and lookups (fhe_direct_group_sum): out[p] has N slots, slot e
+        holds the sum of cols[p] over the right rows j with |left_key_e - right_key_j|
+        < eps.  right_key = left_key: SUM(v) OVER (PARTITION BY key), the row itself
+        included; another table's key and columns: the LEFT JOIN lookup, zero where
+        no right key matches.  count=True: returns (outs, count), the count holding
+        the number of matching right rows.  Equal keys must agree far below eps,
+        distinct keys differ by >= 2 eps, |difference| + eps <= 1, and the sign
+        configuration must resolve eps; 0 < eps < 0.5.  A column may sit at
+        group_sum_levels(...)[0] at most; the outputs end at the rank's level."""
+        r = np.asarray(rots, dtype=np.int32)
+        cols = list(cols)
+        arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
+        outs = (C.c_void_p * max(1, len(cols)))()
+        cnt = C.c_void_p()
+        _chk(lib().fhe_direct_group_sum(self.h, None if left_key is None else left_key.h,
+                                        None if right_key is None else right_key.h, arr, len(cols), float(eps), N,
+                                        _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
+                                        C.byref(cnt) if count else None))
+        res = [Ct(self, outs[i]) for i in range(len(cols))]
+        return (res, Ct(self, cnt.value)) if count else res
+
+    @staticmethod
+    def group_sum_levels(key_level, cfg):
+        return group_sum_levels(key_level, cfg)
+
+    def sub_pm_const_stacked(self, a, bs, c):
+        """stack of 2 len(bs) members: member i is add_const(sub(a, bs[i]), c), member
+        len(bs) + i is add_const(negate(sub(a, bs[i])), c), word for word, in one pass"""
+        ba = (C.c_void_p * max(1, len(bs)))(*[b.h for b in bs])
+        return self._new(lib().fhe_sub_pm_const_stacked, a.h, ba, len(bs), float(c))
+
+    def mul_pairs(self, a, a_add, b_stack, ncols):
+        """the B-member stacks a, a_add against the column-major stack b_stack of
+        ncols * B members: member p * B + z of the result is
+        mul(add(member(a, z), member(a_add, z)), member(b_stack, p * B + z)) word for word"""
+        return self._new(lib().fhe_mul_pairs, a.h, a_add.h, b_stack.h, ncols)
+
     def mul_columns(self, a, cols):
         """the stack a (B members) times each single ciphertext of cols: member
         p * B + z of the result is mul(member(a, z), cols[p]) word for word"""
@@ -1111,6 +1155,16 @@ def size_parameters(N):
     if m < 0:
         raise FheError(-m, lib().fhe_last_error().decode())
     return d.value, [int(x) for x in rots[:m]]
+
+
+def group_sum_levels(key_level, cfg):
+    """fhe_group_sum_levels (pure host): (col_max_level, out_level) of group_sum for
+    keys at key_level under the composite sign cfg = (n, dg, df)"""
+    col, out = C.c_int(), C.c_int()
+    rc = lib().fhe_group_sum_levels(int(key_level), cfg[0], cfg[1], cfg[2], C.byref(col), C.byref(out))
+    if rc != FHE_OK:
+        raise FheError(rc, lib().fhe_last_error().decode())
+    return col.value, out.value
 
 
 def select_layout(N, num_slots, ntargets):

@@ -379,6 +379,67 @@ int fhe_pt_encode_tiebreak(fhe_ctx *ctx, const int32_t *batches, int count, int 
 int fhe_sub_add_plain_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, const fhe_pt *const *ps,
                               int count, fhe_ct **out);
 
+/* Group sums and lookups over rows with equal keys (the project's own extension,
+ * like fhe_direct_select).  left_key, right_key and every column
+ * hold N rows in N slots.  outs[p] has N slots; slot e holds
+ *     sum_j [ |left_key_e - right_key_j| < eps ] cols[p]_j,   j = 0 .. N - 1,
+ * and *count_out (optional) the same sum without the column: the number of
+ * matching right rows.  With right_key = left_key this is SUM(v) OVER (PARTITION
+ * BY key) and COUNT(*) per key, the row itself being part of its group; with a
+ * second table's key and columns it is the lookup of SELECT b.v FROM a LEFT JOIN b
+ * ON a.k = b.k, zero where no right key matches (unique right keys give the
+ * matching row's value).  Slot e of every output belongs to left row e.
+ * The computation is constructRank's all-pairs comparison with "equal" in place of
+ * "smaller": the match indicator of a pair is (sign(d + eps) + sign(-d + eps)) / 2
+ * for the difference d, multiplied into the equally shifted column and summed
+ * over the right rows.  The caller guarantees the tie-break's conditions:
+ *   - equal keys are equal up to noise far below eps,
+ *   - distinct keys differ by at least 2 eps,
+ *   - |left_key_e - right_key_j| + eps <= 1, the sign's domain,
+ *   - the sign configuration (n, dg, df) resolves eps,
+ * and 0 < eps < 0.5.  Levels (fhe_group_sum_levels): with the keys at level k and
+ * the sign consuming D levels, the differences sit at k + 1, the indicator at
+ * L_m = k + 1 + D, a column may sit at col_max_level = L_m - 2 at most (it is
+ * halved on its way to L_m - 1 and meets the indicator after one masked sum), and
+ * every output ends at out_level = L_m + 1, where fhe_direct_sort mode 1 ends: the
+ * depth of any context built for the sort suffices.  rots are the sort's rotation
+ * keys (fhe_size_parameters(N)).  The batches run stacked in chunks of
+ * fhe_set_sort_stack on fhe_set_sort_lanes lanes, the columns in groups bounded by
+ * fhe_set_sort_column_members; the result does not depend on any of them, nor on
+ * fhe_set_mask_cache (0: the call re-encodes the cached masks at its start).
+ * Unsharded.  fhe_set_sort_tiebreak has no effect here.
+ * FHE_EINVAL (the message names the column where one is at fault) for a null key,
+ * a key or column that is a stack, slot counts that differ, keys at different
+ * levels, eps outside (0, 0.5), ncols < 0, a null column, and ncols == 0 without
+ * count_out; FHE_EDEPTH, before any work, for a column above col_max_level and
+ * for a context without out_level levels.  On failure no output handle is set
+ * (every one is NULL). */
+int fhe_direct_group_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *right_key, const fhe_ct *const *cols,
+                         int ncols, double eps, int N, const int32_t *rots, int nrot, int n, int dg, int df,
+                         fhe_ct **outs /* ncols handles */, fhe_ct **count_out /* may be NULL */);
+/* pure host: the levels above for keys at key_level under the composite sign
+ * (n, dg, df), n = 3 or 4 (g_4's series depth taken under the default
+ * Paterson-Stockmeyer split).  Either pointer may be NULL.  FHE_EINVAL for a
+ * negative level or degree or another n. */
+int fhe_group_sum_levels(int key_level, int n, int dg, int df, int *col_max_level, int *out_level);
+/* for tests and bindings: the two-sided differences, member i of the 2 count
+ * stack = fhe_add_const(fhe_sub(a, bs[i]), c) and member count + i =
+ * fhe_add_const(fhe_negate(fhe_sub(a, bs[i])), c) word for word, written by one
+ * kernel from one load of each bs[i], a loaded once per four members
+ * (FHE_GROUP_FUSED=0, read once per process: the stacked differences, then
+ * negate / add_const on the stack).  The bs share a level; a at a lower level is
+ * level-adjusted once, a at a higher one takes per-member operations. */
+int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, int count, double c,
+                             fhe_ct **out);
+/* and the products they feed: a and a_add are stacks of B members, b_stack a
+ * column-major stack of ncols B members, all at one level; member p B + z of the
+ * result = fhe_mul_relin(fhe_add(member z of a, member z of a_add), member p B + z
+ * of b_stack) word for word (one tensor pass that forms a + a_add once per four
+ * columns; FHE_GROUP_FUSED=0: ncols fhe_mul_add products with a_add, stacked).
+ * FHE_EINVAL for member counts or levels that do not fit. */
+int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_ct *b_stack, int ncols,
+                  fhe_ct **out_stack);
+
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
  * grows with it).  Results do not depend on it. */
