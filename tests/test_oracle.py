@@ -5,8 +5,11 @@ Pins, in order of strength:
   1. big-integer golden vectors (tests/golden/, generated from the math by
      make_golden.py): NTT evaluation points/order, negacyclic products,
      coefficient-domain automorphisms;
-  2. exact properties: fast basis conversion = x + u*Q with 0 <= u < |digit|,
-     ModDown = round-free division by P up to the conversion error;
+  2. exact properties: fast basis conversion = x + u*Q with 0 <= u < |digit|
+     (here, and word for word in tests/test_bigint_model.py), ModDown = the
+     centred division by P, exact outside fp64 ties, rescale, the key switch
+     and the ops built from them against Python integers
+     (tests/bigint_model.py, tests/test_bigint_model.py);
   3. the reference's own tests and tolerances, restated:
        DecomposeTest.cpp:64-74, SignTest.cpp:41-122, CompareTest.cpp:43-63,
        RotationTest.cpp:63-130, SincTest.cpp (indicator on k/(2N)),
