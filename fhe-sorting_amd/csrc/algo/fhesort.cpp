@@ -59,6 +59,18 @@ bool fold_scalars() {
     }();
     return v;
 }
+// FHE_LEAF_CONST_FOLD (A/B, default 1): the constant term of a rescaled
+// Paterson-Stockmeyer leaf is added inside the leaf-sum kernel
+// (Engine::linear_sums_to's consts); 0: one add_const_inplace per leaf behind
+// the rescale -- a copying k_c0_op each, the leaves being views of one
+// allocation.  Same words.
+bool leaf_const_fold() {
+    static const bool v = [] {
+        const char *e = std::getenv("FHE_LEAF_CONST_FOLD");
+        return e ? std::atoi(e) != 0 : true;
+    }();
+    return v;
+}
 
 // Levels OpenFHE's EvalChebyshevSeriesPS consumes for a degree-d series: the
 // reference's multDepth tables (src/sort_algo.h:87-201) budget these, and its
@@ -214,10 +226,15 @@ struct PSEval {
             for (int i : idx) row.push_back((size_t)i < leaves[c].a.size() ? leaves[c].a[i] : 0.0);
             rows.push_back(row);
         }
-        auto outs = cc.linear_sums_to(xs, rows, target, !raw);
+        // the rescaled leaves' constant terms ride the sums (raw sums keep theirs
+        // on mul_add's out_const)
+        const bool fold = !raw && leaf_const_fold();
+        std::vector<double> a0;
+        for (size_t c : chunk) a0.push_back(leaves[c].a[0]);
+        auto outs = cc.linear_sums_to(xs, rows, target, !raw, fold ? &a0 : nullptr);
         for (size_t g = 0; g < chunk.size(); ++g) {
             CtPtr r = std::move(outs[g]);
-            if (!raw && leaves[chunk[g]].a[0] != 0.0) cc.add_const_inplace(r, leaves[chunk[g]].a[0]);
+            if (!raw && !fold && a0[g] != 0.0) cc.add_const_inplace(r, a0[g]);
             ready[chunk[g]] = r;
         }
     }
@@ -583,10 +600,13 @@ struct PSOpenFHE {
             for (int i : idx) row.push_back(P->leaves[c].a[i]);
             rows.push_back(row);
         }
-        auto outs = cc.linear_sums_to(xs, rows, target, !L0.raw);
+        const bool fold = !L0.raw && leaf_const_fold();  // (as PsEval::evaluate_chunk)
+        std::vector<double> a0;
+        for (size_t c : chunk) a0.push_back(P->leaves[c].a[0]);
+        auto outs = cc.linear_sums_to(xs, rows, target, !L0.raw, fold ? &a0 : nullptr);
         for (size_t g = 0; g < chunk.size(); ++g) {
             CtPtr r = std::move(outs[g]);
-            if (!L0.raw && P->leaves[chunk[g]].a[0] != 0.0) cc.add_const_inplace(r, P->leaves[chunk[g]].a[0]);
+            if (!L0.raw && !fold && a0[g] != 0.0) cc.add_const_inplace(r, a0[g]);
             ready[chunk[g]] = r;
         }
     }

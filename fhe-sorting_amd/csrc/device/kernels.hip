@@ -532,7 +532,18 @@ struct MultiLinArgs {
     int64_t K[MLS_G * MLS_M];  // [g][i]
     uint8_t sh[MLS_G * MLS_M];  // K[t] * 2^sh[t]
     int m, G, accumulate;
+    // constants folded in ahead of a rescale (ew_linear_sum_multi's cfold): output g
+    // takes + (Kc[g] 2^shc[g]) q_last on its c0 segments, limbs below cfold (0: none)
+    int64_t Kc[MLS_G];
+    uint8_t shc[MLS_G];
+    int cfold;
+    u64 qlast;
 };
+// (K 2^sh mod q)(q_last mod q) mod q: the term that, added to c0 below the last
+// limb before a rescale by q_last, comes out of it as + K mod q
+__device__ __forceinline__ u64 const_times_qlast(int64_t K, int sh, u64 qlast, const Mod &md) {
+    return mul_barrett(smod(K, sh, md), reduce64(qlast, md), md);
+}
 // One coefficient per lane, G outputs.  Every residue and constant is < 2^60,
 // so both split into 30-bit halves and a term costs four v_mad_u64_u32 with
 // accumulate (mac4, no carries); 16 terms fit the four 64-bit partial sums, so
@@ -543,17 +554,21 @@ struct MultiLinArgs {
 template <int G>
 __global__ __launch_bounds__(NT) void k_linear_sum_multi(MultiLinArgs A, size_t seg, const Mod *mods, int logN) {
     __shared__ Split30 w[G * MLS_M];
+    __shared__ u64 cadd[G];
     const size_t n = (size_t)1 << logN;
     const int l = blockIdx.y;
     const Mod md = mods[l];
     for (int t = threadIdx.x; t < G * MLS_M; t += NT) w[t] = split30((t % MLS_M) < A.m ? smod(A.K[t], A.sh[t], md) : 0);
+    if (threadIdx.x < G)
+        cadd[threadIdx.x] = (A.cfold && !(blockIdx.z & 1) && l < A.cfold)
+                                ? const_times_qlast(A.Kc[threadIdx.x], A.shc[threadIdx.x], A.qlast, md) : 0;
     __syncthreads();
     const size_t k = (size_t)blockIdx.x * NT + threadIdx.x;
     if (k >= n) return;
     const size_t ln = (size_t)l * n + k, oo = (size_t)blockIdx.z * seg + ln;
     Acc128 run[G];
 #pragma unroll
-    for (int g = 0; g < G; ++g) run[g].lo = A.accumulate ? A.out[g][oo] : 0;
+    for (int g = 0; g < G; ++g) run[g].lo = (A.accumulate ? A.out[g][oo] : 0) + cadd[g];  // (both < q < 2^60)
     for (int base = 0; base < A.m; base += 16) {
         const int end = min(A.m, base + 16);
         Acc4 s[G];
@@ -746,7 +761,17 @@ struct LeafArgs {
     const uint8_t *sh;      // device [G][m]
     int m, G, accumulate;
     int six;  // k_leaf_sums_fold: the FP primes' six-digit rows (FHE_LEAF_SIX)
+    // constants folded in ahead of a rescale (ew_linear_sum_multi's cfold): output t
+    // takes + (K[G m + t] 2^sh[G m + t]) q_last on its c0 segments, limbs below cfold
+    // (0: none, and the tables end at G m)
+    int cfold;
+    u64 qlast;
 };
+// the block's folded constant of output t (segment blockIdx.z, limb l), or 0
+__device__ __forceinline__ u64 leaf_const(const LeafArgs &A, int t, int l, const Mod &md) {
+    if (!A.cfold || t >= A.G || (blockIdx.z & 1) || l >= A.cfold) return 0;
+    return const_times_qlast(A.K[A.G * A.m + t], A.sh[A.G * A.m + t], A.qlast, md);
+}
 #ifndef FHE_LF_NC  // 16-coefficient column tiles per wave sharing one set of windows (A/B: -DFHE_LF_NC=4)
 #define FHE_LF_NC 2
 #endif
@@ -783,7 +808,7 @@ __global__ __launch_bounds__(LF_NT) __attribute__((amdgpu_waves_per_eu(FHE_LF_WP
         u64 s = 0;
         if (tid < A.G)
             for (int i = 0; i < A.m; ++i) s = add_mod(s, smod(A.K[tid * A.m + i], A.sh[tid * A.m + i], md), md.q);
-        corr[tid] = sums_constant(s, md);
+        corr[tid] = add_mod(sums_constant(s, md), leaf_const(A, tid, l, md), md.q);
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, col = lane & 15, lg = lane >> 4;
@@ -1044,8 +1069,10 @@ __global__ __launch_bounds__(LFF_NT) __attribute__((amdgpu_waves_per_eu(2, 8))) 
         for (int i = 0; i < A.m; ++i) s = add_mod(s, psum[tid][i], md.q);
         // + 128 sum d (the signed bytes) - 2^126 (fold_rows2's bias)
         const u64 b126 = mul_shoup(reduce64(1ull << 62, md), md.r64, md.r64s, md.q);
-        corr[tid] = sub_mod(mul_barrett(s, 128, md), b126, md.q);
-        cfp[tid] = mul_barrett(s, 128, md);  // (the fp64 epilogue has no bias)
+        // (+ the output's folded constant: both epilogues take any residue below q)
+        const u64 ca = leaf_const(A, tid, l, md);
+        corr[tid] = add_mod(sub_mod(mul_barrett(s, 128, md), b126, md.q), ca, md.q);
+        cfp[tid] = add_mod(mul_barrett(s, 128, md), ca, md.q);  // (the fp64 epilogue has no bias)
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, col = lane & 15, lg = lane >> 4;
@@ -3120,7 +3147,7 @@ int leaf_fold_enabled() {
 bool linear_sums_on_mfma(int logN) { return use_mfma_sums(MF_LIN) && logN >= 8; }
 void ew_linear_sum_multi(u64 *const *outs, int G, const u64 *const *xs, const size_t *xseg, const int64_t *K, int m,
                          int limbs, int segs, size_t seg, const Mod *mods, int logN, hipStream_t st,
-                         const uint8_t *sh, const int64_t *dK, const uint8_t *dsh) {
+                         const uint8_t *sh, const int64_t *dK, const uint8_t *dsh, int cfold, u64 qlast) {
     if (limbs <= 0 || segs <= 0 || G <= 0 || m <= 0) return;
     if (G > LEAF_G) throw std::invalid_argument("ew_linear_sum_multi: at most LEAF_G outputs per call");
     const size_t n = (size_t)1 << logN;
@@ -3140,6 +3167,8 @@ void ew_linear_sum_multi(u64 *const *outs, int G, const u64 *const *xs, const si
             }
             A.K = dK;
             A.sh = dsh;
+            A.cfold = cfold;
+            A.qlast = qlast;
             const double B = 8.0 * (A.m + (double)G * (1 + A.accumulate)) * limbs * segs * (double)n;
             size_t ch = std::min<size_t>(LS_CH_MAX, n);
             while (ch > 256 && (n / ch) * (size_t)limbs * (size_t)segs < 2048) ch /= 2;
@@ -3177,6 +3206,12 @@ void ew_linear_sum_multi(u64 *const *outs, int G, const u64 *const *xs, const si
             A.m = std::min(MLS_M, m - base);
             A.G = Gp;
             A.accumulate = base > 0;
+            A.cfold = base == 0 ? cfold : 0;  // (a sum of more than MLS_M inputs takes its constant once)
+            A.qlast = qlast;
+            for (int g = 0; g < Gp && cfold; ++g) {
+                A.Kc[g] = K[(size_t)G * m + g0 + g];
+                A.shc[g] = sh ? sh[(size_t)G * m + g0 + g] : 0;
+            }
             for (int g = 0; g < Gp; ++g) A.out[g] = outs[g0 + g];
             for (int i = 0; i < A.m; ++i) {
                 A.x[i] = xs[base + i];

@@ -138,6 +138,9 @@ struct NttFuse {
     size_t seg_d2 = 0;
     const u64 *key = nullptr;
     int nall = 0;
+    // looped lifted column pass (set at launch): block z runs the grid limbs
+    // z * zchunk .. min((z + 1) * zchunk, zcount) - 1
+    int zchunk = 1, zcount = 0;
 };
 // inverse NTT reading the input from `src` (segment z, limb l at src + z*seg_src + l*n), writing dst
 void ntt_inverse_from(u64 *dst, const u64 *src, size_t seg_src, int limbs, int segs, size_t seg, const int *pmap,
@@ -230,10 +233,14 @@ void ew_linear_sum(u64 *out, const u64 *const *xs, const int64_t *K, int m, int 
 // constants then come from the device copies dK / dsh of K / sh ([G][m]).  The
 // VALU kernel (mask bit clear, no device copies, or m > 64) takes passes of
 // <= 10 outputs x 32 inputs from the host arrays.
+// cfold > 0 (sums that a rescale by the prime qlast follows): K / sh and their
+// device copies carry G more entries, the constant C_g = K[G m + g] 2^sh[G m + g]
+// of output g, and the sum's c0 segments (even) take + C_g qlast on the limbs
+// below cfold -- after the rescale that is + C_g mod q_l, add_const's words.
 constexpr int LEAF_G = 32, LEAF_M = 64;
 void ew_linear_sum_multi(u64 *const *outs, int G, const u64 *const *xs, const size_t *xseg, const int64_t *K, int m,
                          int limbs, int segs, size_t seg, const Mod *mods, int logN, hipStream_t st,
-                         const uint8_t *sh, const int64_t *dK, const uint8_t *dsh);
+                         const uint8_t *sh, const int64_t *dK, const uint8_t *dsh, int cfold = 0, u64 qlast = 0);
 // true iff ew_linear_sum_multi runs on the matrix cores at this ring (it then reads dK / dsh)
 bool linear_sums_on_mfma(int logN);
 // out [members][2][limbs][n] = sum_i ct_i * pt_i  (ct_i member stride cmember, 0 = broadcast;

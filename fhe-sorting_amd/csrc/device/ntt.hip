@@ -587,9 +587,15 @@ enum { NTT_PLAIN = 0, NTT_LIFT = 1, NTT_RESCALE = 2, NTT_MULTAIL = 3, NTT_KSFINI
 // ROWS: the transform index is a row `hi`, element idx sits at hi * 2^PB + idx.
 // SH (row passes with PB = 8 only): register-only stages with DPP lane swaps
 // (row_pass_shfl) instead of the two LDS exchanges.
-template <int PB, int EB, bool COLS, int MODE, bool SH, bool FULL, bool TWL = false, bool FP = false>
+// LOOPED (the lifted column pass of k_ntt_lift_loop): the caller holds the
+// block's tile of `last` in `raw` (already times K mod q_last when the rescale
+// is scaled) and calls the body once per target limb zi of its launch.
+template <int PB, int EB, bool COLS, int MODE, bool SH, bool FULL, bool TWL = false, bool FP = false,
+          bool LOOPED = false>
 __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *pmap, const int *smap, int logN,
-                                             const NttTables &Tb, const NttFuse &F) {
+                                             const NttTables &Tb, const NttFuse &F, const int zi,
+                                             const u64 *raw = nullptr) {
+    static_assert(!LOOPED || (COLS && MODE == NTT_LIFT), "looped body: the lifted column pass");
     static_assert(!SH || (!COLS && PB == 8 && EB == 4), "shuffle row pass: 16 lanes x 16 coefficients");
     constexpr int E = 1 << EB;          // coefficients per lane
     constexpr int RB = PB - EB;         // bits of round 2
@@ -611,7 +617,7 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
     // grid: x = segment (fastest, so the blocks of one prime's row/column
     // block across all segments run back to back and share its twiddles in
     // L2), y = block within the limb, z = limb (through the launch's limb runs)
-    const int limb = F.limb_of(blockIdx.z);
+    const int limb = F.limb_of(zi);
     const int p = pmap ? __builtin_amdgcn_readfirstlane(pmap[limb]) : limb;
     int t, tr;  // lane within its transform, transform within the block
     if (COLS) {
@@ -649,7 +655,11 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
 
     u64 x[E];
     // ---- load, layout L1: idx = t + T * r
-    if (MODE == NTT_LIFT) {
+    if constexpr (LOOPED) {
+        const u64 ql = Tb.mods[F.lastp].q, qh = ql >> 1;
+#pragma unroll
+        for (int r = 0; r < E; ++r) x[r] = raw[r] > qh ? q - (ql - raw[r]) : raw[r];
+    } else if (MODE == NTT_LIFT) {
         // centred lift of c mod q_last into prime p: q_last / 2 < q_p (checked at
         // context creation), so c or q_p - (q_last - c) is already reduced
         const Mod ml = Tb.mods[F.lastp];
@@ -1142,7 +1152,43 @@ __device__ __forceinline__ void ntt_inv_body(u64 *data, size_t seg, const int *p
 template <int PB, int EB, bool COLS, int MODE, bool FULL, bool FP>
 __global__ __launch_bounds__((nthreads<PB, COLS>())) __attribute__((amdgpu_waves_per_eu(COLS ? FHE_NTT_COL_WPE : 1, 8))) void k_ntt_fwd(
     u64 *data, size_t seg, const int *pmap, const int *smap, int logN, NttTables Tb, NttFuse F) {
-    ntt_fwd_body<PB, EB, COLS, MODE, false, FULL, false, FP>(data, seg, pmap, smap, logN, Tb, F);
+    ntt_fwd_body<PB, EB, COLS, MODE, false, FULL, false, FP>(data, seg, pmap, smap, logN, Tb, F, blockIdx.z);
+}
+// The lifted column pass of a rescale with the limb loop inside the block
+// (FHE_RESCALE_LIFT_LOOP): k_ntt_fwd<.., NTT_LIFT, ..> loads the block's tile of
+// `last` once per target limb, and at a stacked rescale (`last` far larger than
+// the caches) every one of those loads comes from memory.  Here a block loads
+// the tile once, keeps the E raw words per lane (times K mod q_last, when the
+// rescale is scaled: that product does not depend on the target) and runs the
+// lift, the butterflies and the store for the F.zchunk limbs
+// blockIdx.z * zchunk .. of the launch's F.zcount.  Same words as the per-limb
+// form.  The barrier between two limbs keeps a fast wave's next stores to the
+// exchange tile (and the staged twiddles) behind the slow waves' last reads.
+// Exact grids only (the launch checks it): with the bounds checks the loop keeps
+// every store address live in VGPR pairs (ring 2^16, fp64: 164 VGPRs, 3 waves per
+// SIMD, against 126 and 4 with the buffer-addressed stores of the exact form).
+template <int PB, int EB, bool FP>
+__global__ __launch_bounds__((nthreads<PB, true>())) __attribute__((amdgpu_waves_per_eu(FHE_NTT_COL_WPE, 8))) void k_ntt_lift_loop(
+    u64 *data, size_t seg, const int *pmap, const int *smap, int logN, NttTables Tb, NttFuse F) {
+    constexpr int E = 1 << EB, T = 1 << (PB - EB), NB = nthreads<PB, true>() / T;
+    const int k2 = logN - PB;
+    const int tr = threadIdx.x % NB, t = threadIdx.x / NB;
+    const size_t col = (size_t)blockIdx.y * NB + tr;
+    const u64 *src = F.last + (size_t)blockIdx.x * F.seg_last;
+    const Mod ml = Tb.mods[F.lastp];
+    const u64 kl = F.scalar ? smod64(F.scalar, F.scalar_sh, ml) : 0;  // K mod q_last (scaled rescale)
+    u64 raw[E];
+#pragma unroll
+    for (int r = 0; r < E; ++r) {
+        u64 c = src[((size_t)(t + T * r) << k2) + col];
+        if (F.scalar) c = mul_barrett(c, kl, ml);
+        raw[r] = c;
+    }
+    const int z0 = (int)blockIdx.z * F.zchunk, z1 = min(z0 + F.zchunk, F.zcount);
+    for (int z = z0; z < z1; ++z) {
+        if (z != z0) __syncthreads();
+        ntt_fwd_body<PB, EB, true, NTT_LIFT, false, true, false, FP, true>(data, seg, pmap, smap, logN, Tb, F, z, raw);
+    }
 }
 template <int PB, int EB, bool COLS, bool FULL, bool FP>
 __global__ __launch_bounds__((nthreads<PB, COLS>())) __attribute__((amdgpu_waves_per_eu(COLS ? FHE_NTT_COL_WPE : 1, 8))) void k_ntt_inv(
@@ -1166,7 +1212,7 @@ __global__ __launch_bounds__((nthreads<PB, COLS>())) __attribute__((amdgpu_waves
 template <int MODE, bool FULL, bool TWL, bool FP>
 __global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(FP ? (MODE == NTT_RESCALE ? FHE_NTT_FP_RESCALE_WPE : FHE_NTT_FP_ROW_WPE) : TWL ? FHE_NTT_ROW_WPE : 1, 8))) void k_ntt_fwd_row(
     u64 *data, size_t seg, const int *pmap, const int *smap, int logN, NttTables Tb, NttFuse F) {
-    ntt_fwd_body<8, 4, false, MODE, true, FULL, TWL, FP>(data, seg, pmap, smap, logN, Tb, F);
+    ntt_fwd_body<8, 4, false, MODE, true, FULL, TWL, FP>(data, seg, pmap, smap, logN, Tb, F, blockIdx.z);
 }
 template <bool FULL, bool TWL, bool FP>
 __global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(TWL ? FHE_NTT_ROW_WPE : 1, 8))) void k_ntt_inv_row(
@@ -1379,6 +1425,32 @@ constexpr int full_bit() {
                : (COLS ? 32 : 64);
 }
 
+// FHE_RESCALE_LIFT_LOOP (default 1): the lifted column pass of a rescale runs
+// as k_ntt_lift_loop, which loads the last limb's tile once per block and loops
+// over target limbs, wherever that leaves the chip enough blocks; 0 keeps one
+// block per (tile, limb) everywhere (k_ntt_fwd<.., 1, ..>).  Same words.
+int &lift_loop_enabled() {
+    static int v = [] {
+        const char *e = std::getenv("FHE_RESCALE_LIFT_LOOP");
+        return e ? std::atoi(e) : 1;
+    }();
+    return v;
+}
+// FHE_RESCALE_LIFT_MIN_BLOCKS: fewest blocks a looped launch may have.  The
+// limbs of a launch are cut into as many chunks per tile as it takes to reach
+// it; a launch that would need one chunk per limb stays on the per-limb kernel.
+// The default is two rounds of the chip's resident blocks (256 CUs x 4 blocks of
+// 4 waves): a one-member rescale at ring 2^16 (2 x 16 tiles) keeps the per-limb
+// grid, a 32-member one (64 x 16 tiles) reads `last` twice, the 2,048-segment
+// leaf rescales of the sort once.
+int &lift_loop_min_blocks() {
+    static int v = [] {
+        const char *e = std::getenv("FHE_RESCALE_LIFT_MIN_BLOCKS");
+        return e ? std::max(1, std::atoi(e)) : 2048;
+    }();
+    return v;
+}
+
 template <int PB, int EB, bool COLS, bool FWD, int MODE, bool FP>
 void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap, const int *smap, const NttTables &T,
                      const NttFuse &F, hipStream_t st) {
@@ -1405,10 +1477,25 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
                     (unsigned)limbs);
         full = want_full && count % rows_pb == 0 && segs % (1 << Fs.lsegb) == 0;
     }
+    // looped lifted column pass: `limbs` target limbs in chunks of zchunk per block
+    // (rings 2^11 .. 2^16: smaller column passes hold too few words to matter, and
+    // at ring 2^17 the 32 raw words per lane on top of the pass's own 126 - 168
+    // VGPRs leave one or two waves per SIMD).  The looped kernel has the exact
+    // grid only, whatever ntt_full_mask says for the per-limb form.
+    constexpr bool CAN_LOOP = COLS && FWD && MODE == NTT_LIFT && PB >= 6 && PB <= 8;
+    bool loop = false;
+    if (CAN_LOOP && limbs > 1 && count % NB == 0 && lift_loop_enabled() != 0) {
+        const long tiles = (long)grid.x * grid.y;
+        const long nz = std::min<long>(limbs, (lift_loop_min_blocks() + tiles - 1) / tiles);
+        Fs.zchunk = (int)((limbs + nz - 1) / nz);
+        Fs.zcount = limbs;
+        loop = Fs.zchunk > 1;
+        if (loop) grid.z = (unsigned)((limbs + Fs.zchunk - 1) / Fs.zchunk);
+    }
     LaunchClock *clk = launch_clock();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const int slot = clk ? clk->events(e0, e1) : -1;
-    note_launch(FWD ? (COLS ? "k_ntt_fwd(col)" : "k_ntt_fwd(row)") : (COLS ? "k_ntt_inv(col)" : "k_ntt_inv(row)"), grid,
+    note_launch(loop ? "k_ntt_lift_loop(col)" : FWD ? (COLS ? "k_ntt_fwd(col)" : "k_ntt_fwd(row)") : (COLS ? "k_ntt_inv(col)" : "k_ntt_inv(row)"), grid,
                 dim3(NTHR));
     // staged row twiddles (dynamic LDS: the block's 16 >> lsegb rows x 256 entries)
     // when a block holds at most row_twl_rows() rows
@@ -1417,7 +1504,9 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
     const unsigned lds_dyn = twl ? (unsigned)(rows_blk * 256 * (FP ? sizeof(double) : sizeof(TwT<false>))) : 0u;
 #define FHE_NTT_LAUNCH(K, FF) \
     hipExtLaunchKernelGGL((K), grid, dim3(NTHR), lds_dyn, st, e0, e1, 0, data, seg, pmap, smap, T.logN, T, FF)
-    if (FWD && sh) {
+    if (loop) {
+        if constexpr (CAN_LOOP) FHE_NTT_LAUNCH((k_ntt_lift_loop<PB, EB, FP>), Fs);
+    } else if (FWD && sh) {
         if (full && twl) FHE_NTT_LAUNCH((k_ntt_fwd_row<MODE, true, true, FP>), Fs);
         else if (full) FHE_NTT_LAUNCH((k_ntt_fwd_row<MODE, true, false, FP>), Fs);
         else if (twl) FHE_NTT_LAUNCH((k_ntt_fwd_row<MODE, false, true, FP>), Fs);
@@ -1442,7 +1531,8 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
         const std::string pe = std::to_string(PB) + ", " + std::to_string(EB) + (COLS ? ", true" : ", false");
         const std::string fl = (full ? "true, " : "false, ") + fps;
         const std::string fl2 = (full ? "true, " : "false, ") + std::string(twl ? "true, " : "false, ") + fps;
-        const std::string base = FWD && sh ? "k_ntt_fwd_row<" + std::to_string(MODE) + ", " + fl2
+        const std::string base = loop      ? "k_ntt_lift_loop<" + std::to_string(PB) + ", " + std::to_string(EB) + ", " + fps
+                                 : FWD && sh ? "k_ntt_fwd_row<" + std::to_string(MODE) + ", " + fl2
                                  : FWD     ? "k_ntt_fwd<" + pe + ", " + std::to_string(MODE) + ", " + fl
                                  : sh      ? "k_ntt_inv_row<" + fl2
                                            : "k_ntt_inv<" + pe + ", " + fl;
@@ -1458,8 +1548,10 @@ void launch_pass_one(u64 *data, int limbs, int segs, size_t seg, const int *pmap
         const double extra = MODE == NTT_RESCALE ? 1.0 : MODE == NTT_MULTAIL ? 2.0
                              : MODE == NTT_KSFINISH || MODE == NTT_MULTAIL_OWN ? 1.5 : 0.0;
         const double once = MODE == NTT_MULTAIL_OWN ? 2.0 : 0.0;
-        clk->record(slot, it->second.c_str(),
-                    ((2.0 + extra) * segs + once) * 8.0 * (double)limbs * ((size_t)1 << T.logN));
+        // (looped lift: the last limb once, every target written once)
+        const double bytes = loop ? (double)(limbs + 1) * segs * 8.0 * ((size_t)1 << T.logN)
+                                  : ((2.0 + extra) * segs + once) * 8.0 * (double)limbs * ((size_t)1 << T.logN);
+        clk->record(slot, it->second.c_str(), bytes);
     }
 }
 

@@ -2380,11 +2380,20 @@ CtPtr Engine::linear_sum_to(const std::vector<const Ciphertext *> &xs, const std
 // gives the coefficients of output g.  Equal, word for word, to one
 // linear_sum_to per row, but each input is streamed once per pass of up to
 // 10 outputs.
+// consts (rescaled sums only): output g is add_const(sum_g, (*consts)[g]) word
+// for word.  The rescale is linear in c0 and divides by q_last, so the sum
+// kernel adds K_g q_last mod q_l, K_g = const_at_scale(c, delta[target]), to c0
+// on the limbs below the last (the last limb, all the rescale reads of it, stays
+// what it was) and the rescale stores add_const's canonical words: no pass and
+// no copy per output (mul_add's out_const does the same in the tensor pass).
 std::vector<CtPtr> Engine::linear_sums_to(const std::vector<const Ciphertext *> &xs,
-                                          const std::vector<std::vector<double>> &c, int target, bool rescale) {
+                                          const std::vector<std::vector<double>> &c, int target, bool rescale,
+                                          const std::vector<double> *consts) {
     auto &I = *impl;
     if (target > I.P.L) throw std::runtime_error("linear_sums_to: no levels left");
     if (xs.empty()) throw std::invalid_argument("linear_sums_to: no inputs");
+    if (consts && !rescale) throw std::invalid_argument("linear_sums_to: constants go with rescaled sums only");
+    if (consts && consts->size() != c.size()) throw std::invalid_argument("linear_sums_to: one constant per output");
     const int B = xs[0]->batch, segs = 2 * B;
     const size_t nn = n(), ell = I.P.limbs_at(target - 1), m = xs.size();
     const u64 qd = I.P.primes[I.P.L - target + 1];
@@ -2403,8 +2412,16 @@ std::vector<CtPtr> Engine::linear_sums_to(const std::vector<const Ciphertext *> 
     const bool mfma = dev::linear_sums_on_mfma(LOGN) && m <= (size_t)dev::LEAF_M;
     for (size_t g0 = 0; g0 < c.size(); g0 += per) {
         const int G = (int)std::min<size_t>(per, c.size() - g0);
-        std::vector<int64_t> K((size_t)G * m);
-        std::vector<uint8_t> sh((size_t)G * m);
+        // (with constants: G more entries behind the [G][m] rows, ew_linear_sum_multi's cfold)
+        std::vector<int64_t> K((size_t)G * m + (consts ? G : 0));
+        std::vector<uint8_t> sh((size_t)G * m + (consts ? G : 0));
+        for (int g = 0; g < G && consts; ++g) {
+            const double cg = (*consts)[g0 + g];
+            const host::SConst k = cg != 0.0 ? host::const_at_scale(cg, I.P.delta[target]) : host::SConst{};
+            K[(size_t)G * m + g] = k.k;
+            sh[(size_t)G * m + g] = (uint8_t)k.sh;
+            if (cg != 0.0) count_bytes(4.0 * (ell - 1), B);  // the add_const copy it replaces
+        }
         for (int g = 0; g < G; ++g) {
             if (c[g0 + g].size() != m) throw std::invalid_argument("linear_sums_to: coefficient row size");
             for (size_t i = 0; i < m; ++i) {
@@ -2420,7 +2437,7 @@ std::vector<CtPtr> Engine::linear_sums_to(const std::vector<const Ciphertext *> 
         std::pair<const int64_t *, const uint8_t *> dk{nullptr, nullptr};
         if (mfma) dk = I.const_table(K, sh);
         dev::ew_linear_sum_multi(op.data(), G, xp.data(), xseg.data(), K.data(), (int)m, (int)ell, segs, ell * nn,
-                                 MODS, LOGN, ST, sh.data(), dk.first, dk.second);
+                                 MODS, LOGN, ST, sh.data(), dk.first, dk.second, consts ? (int)ell - 1 : 0, qd);
         if (!rescale) {  // raw sums at the pre-rescale scale, views into one allocation
             for (int g = 0; g < G; ++g) {
                 auto r = std::make_shared<Ciphertext>();

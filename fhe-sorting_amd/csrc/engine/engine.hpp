@@ -306,8 +306,11 @@ class Engine {
     CtPtr linear_sum_to(const std::vector<const Ciphertext *> &xs, const std::vector<double> &c, int target);
     // several linear sums of the same inputs (PS leaves): one output per row of c
     // (rescale = false: the raw sums at level target-1 and the pre-rescale scale, for mul_add_raw)
+    // consts (rescaled sums only): one constant per output, added as add_const would
+    // add it, inside the sum kernel (no pass of its own)
     std::vector<CtPtr> linear_sums_to(const std::vector<const Ciphertext *> &xs,
-                                      const std::vector<std::vector<double>> &c, int target, bool rescale = true);
+                                      const std::vector<std::vector<double>> &c, int target, bool rescale = true,
+                                      const std::vector<double> *consts = nullptr);
     CtPtr trivial_const(double c, int level, int slots, int batch = 1);
     CtPtr zero_like(int level, int slots, int batch = 1);
     // batches: stack (copies; equal levels), member view (no copy), member sum
