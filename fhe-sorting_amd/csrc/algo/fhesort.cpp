@@ -2013,6 +2013,123 @@ std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext
     return outs;
 }
 
+LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split) {
+    if (nkeys < 2 || nkeys > 4) throw std::invalid_argument("lex rank: 2 to 4 keys, got " + std::to_string(nkeys));
+    const GroupSumLevels g = groupSumLevels(key_level, n, dg, df, ps_split);  // the same differences and sign
+    LexRankLevels lv;
+    lv.sign_depth = g.sign_depth;
+    lv.diff_level = g.diff_level;
+    lv.sign_level = g.match_level;
+    lv.rank_level = lv.sign_level + nkeys;
+    return lv;
+}
+
+// Lexicographic rank.  constructRank's layout, key by key: slot s of batch b holds
+// K_l[s mod N] - K_l[(s mod N + t) mod N], t = b P_ + s / N, for every key l, so the
+// Horner recurrence runs slot-wise on the sign outputs of one pair.  The factors
+// of 1/2 of the L indicators are postponed to the closing 2^-L.
+CtPtr DirectSortN::lexRank(const std::vector<const Ciphertext *> &keys, double eps, SignFunc f,
+                           const SignConfig &cfg) {
+    const SortShape s = rankShape(N, max_batch);
+    const int L = (int)keys.size();
+    if (L < 2 || L > 4) throw std::invalid_argument("lex rank: 2 to 4 keys, got " + std::to_string(L));
+    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("lex rank: eps must lie in (0, 0.5)");
+    for (int l = 0; l < L; ++l) {
+        const std::string which = "lex rank: key " + std::to_string(l);
+        if (!keys[l]) throw std::invalid_argument(which + " is null");
+        if (keys[l]->batch != 1) throw std::invalid_argument(which + " is a stack");
+        if (keys[l]->slots != keys[0]->slots)
+            throw std::invalid_argument(which + " has " + std::to_string(keys[l]->slots) + " slots, key 0 " +
+                                        std::to_string(keys[0]->slots));
+        if (keys[l]->level != keys[0]->level)
+            throw std::invalid_argument(which + " sits at level " + std::to_string(keys[l]->level) + ", key 0 at level " +
+                                        std::to_string(keys[0]->level));
+    }
+    const LexRankLevels lv =
+        lexRankLevels(keys[0]->level, L, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
+    if (lv.rank_level > cc.params().L)
+        throw std::runtime_error("lex rank: " + std::to_string(L) + " keys at level " + std::to_string(keys[0]->level) +
+                                 " need " + std::to_string(lv.rank_level) + " levels, the context has " +
+                                 std::to_string(cc.params().L) + ": no levels left");
+    if (!cache_masks) refresh_masks();
+    std::optional<AlgoPhase> ph;
+    ph.emplace("lex_baby");
+    std::vector<std::vector<CtPtr>> baby(L);
+    std::vector<CtPtr> dups(L);
+    for (int l = 0; l < L; ++l) {
+        baby[l] = babySteps(*keys[l], s.np);
+        for (auto &b : baby[l]) b->slots = s.num_slots;
+        dups[l] = cc.clone(*keys[l]);
+        dups[l]->slots = s.num_slots;
+    }
+    ph.reset();
+    std::vector<int> mine(s.num_batch);
+    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
+    // the last key's tie-break offsets, at the level the differences sit at
+    std::map<int, PtPtr> offs;
+    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0][0]->level + 1);
+    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
+    // a chunk's sign runs over (2 L - 1) members per batch: the plain rank's footprint
+    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / (2 * L - 1));
+    std::vector<const Ciphertext *> dp;
+    for (auto &d : dups) dp.push_back(d.get());
+    auto parts = run_lanes(mine, [&](Lane Ln, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *Ln.eng;
+        AlgoPhase lane_ph("lex_batches");
+        CtPtr acc;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr sg;
+            {
+                std::vector<CtPtr> shifted;  // key-major
+                for (int l = 0; l < L; ++l)
+                    for (auto &x : vecRotsOptMany(Ln, baby[l], s.num_partition, s.num_slots, s.np, iss))
+                        shifted.push_back(x);
+                std::vector<const Ciphertext *> ptrs;
+                for (auto &x : shifted) ptrs.push_back(x.get());
+                std::vector<const Plaintext *> es;
+                if (tiebreak > 0.0)
+                    for (int b : iss) es.push_back(offs.at(b).get());
+                CtPtr d = E.sub_lex_stacked(dp, ptrs, es, eps);
+                shifted.clear();
+                sg = sign(*d, E, f, cfg);
+            }
+            if (sg->level != lv.sign_level) throw std::logic_error("lex rank: unexpected sign output level");
+            auto view = [&](int first) {  // B members of the sign's stack from member `first` on
+                Ciphertext v = *sg;
+                v.batch = B;
+                v.data = sg->data + (size_t)first * 2 * sg->limbs * E.n();
+                return v;
+            };
+            // Horner, innermost key first: T = (u_l - w_l) (T [+ 1]) + 2^(L-1-l) (w_l + 1)
+            CtPtr T;
+            for (int l = L - 2; l >= 0; --l) {
+                const Ciphertext u = view(2 * l * B), w = view((2 * l + 1) * B);
+                CtPtr prod = l == L - 2 ? E.mul_lex(view(2 * (L - 1) * B), 1.0, u, w) : E.mul_lex(*T, 0.0, u, w);
+                CtPtr sm = E.mul_const_to(*E.add_const(w, 1.0), (double)(1 << (L - 1 - l)), prod->level);
+                T = E.add(*prod, *sm);
+            }
+            E.add_inplace(acc, B == 1 ? *T : *E.sum_members(*T));
+        }
+        return acc;
+    });
+    CtPtr rank;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(rank, *p);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    ph.emplace("lex_fold");
+    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+        rank = cc.add(*rank, *rot.rotate(*rank, s.num_slots / (1 << i)));
+    rank = cc.mul_const(*rank, 1.0 / (double)(1 << L));
+    // the self comparison: 1/2 at sign(0) on the last key, a clean 1 with the tie-break offset
+    cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5);
+    rank->slots = N;
+    if (rank->level != lv.rank_level) throw std::logic_error("lex rank: unexpected output level");
+    return rank;
+}
+
 // Re-encodes every cached mask (the reference's per-use encoding,
 // src/sort_algo.h:341-342, 714-716) for sort() with mask caching off.  Chunks
 // of REFRESH_CHUNK masks: each chunk's new plaintexts replace (and release) old

@@ -199,6 +199,17 @@ struct GroupSumLevels {
 };
 GroupSumLevels groupSumLevels(int key_level, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
 
+// Levels of DirectSortN::lexRank for nkeys keys (2..4) at key_level under the
+// composite sign (n, dg, df): the differences at diff_level = key_level + 1, every
+// sign output at sign_level = diff_level + sign_depth, one level per Horner step
+// and one for the closing 2^-nkeys, so the rank ends at rank_level = sign_level +
+// nkeys: nkeys - 1 levels below constructRank's.  Throws std::invalid_argument on
+// a key count outside 2..4, a negative level or a sign the GPU path lacks.
+struct LexRankLevels {
+    int sign_depth, diff_level, sign_level, rank_level;
+};
+LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
+
 // Sums a ciphertext's u64 limbs over ranks in place (device pointer, count
 // u64); the engine reduces mod q afterwards.  nullptr = single rank.
 using CtAllReduce = std::function<void(u64 *dev_data, size_t count)>;
@@ -289,6 +300,26 @@ class DirectSortN {
     // Unsharded; `tiebreak` has no effect.
     std::vector<CtPtr> groupSums(const Ciphertext &kl, const Ciphertext &kr, const std::vector<const Ciphertext *> &cols,
                                  double eps, bool want_count, SignFunc f, const SignConfig &cfg);
+    // Lexicographic rank (the project's own extension): the rank of
+    // row e among the N rows ordered by keys[0], then keys[1], ... (2..4 keys, most
+    // significant first, single ciphertexts of N slots at one level).  With
+    // d_l = K_l[e] - K_l[j] per pair: u_l = sign(d_l + eps), w_l = sign(d_l - eps) on the
+    // leading keys, s = sign(d_{L-1} + E) on the last (E the tie-break offset when
+    // `tiebreak` is set), T_{L-1} = s + 1, T_l = (u_l - w_l) T_{l+1} + 2^{L-1-l} (w_l + 1),
+    // rank_e = 2^-L sum_j T_0 - c, c = 1 with the tie-break (the stable lexicographic
+    // argsort rank) and 1/2 without (rows tied on every key behave as the plain
+    // rank's ties).  constructRank's all-pairs layout with one set of baby steps
+    // per key and the rank's own masks; a chunk of B = max(1, max_stack / (2 L - 1))
+    // batches runs one sign over a (2 L - 1) B stack (Engine::sub_lex_stacked) and
+    // the Horner steps as stacked products (Engine::mul_lex).  Needs values equal on
+    // a leading key equal far below eps, distinct ones >= 2 eps apart, |d| + eps <= 1,
+    // a sign configuration that resolves eps, and the tie-break's conditions on the
+    // last key.  Levels: lexRankLevels; a context without rank_level levels is
+    // refused before any work.  The words do not depend on max_stack, lanes or
+    // cache_masks (false: the call re-encodes what it caches at its start).
+    // Unsharded.  The result feeds rotationIndexCheckN / rotationIndexCheckColumns /
+    // selectColumns as any rank does.
+    CtPtr lexRank(const std::vector<const Ciphertext *> &keys, double eps, SignFunc f, const SignConfig &cfg);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;

@@ -811,6 +811,88 @@ int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_
         *out_stack = wrap(ctx->eng->mul_pairs(*a->p, *a_add->p, *b_stack->p, ncols));
     });
 }
+int fhe_direct_lex_rank(fhe_ctx *ctx, const fhe_ct *const *keys, int nkeys, double eps, int N, const int32_t *rots,
+                        int nrot, int n, int dg, int df, fhe_ct **rank) {
+    if (rank) *rank = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        NEED(rank);
+        if (nkeys < 2 || nkeys > 4)
+            throw std::invalid_argument("fhe_direct_lex_rank: nkeys must lie in 2..4, got " + std::to_string(nkeys));
+        NEED(keys);
+        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_lex_rank: eps must lie in (0, 0.5)");
+        std::vector<const Ciphertext *> v;
+        for (int l = 0; l < nkeys; ++l) {
+            const std::string which = "fhe_direct_lex_rank: key " + std::to_string(l);
+            if (!keys[l] || !keys[l]->p) throw std::invalid_argument(which + " is null");
+            const Ciphertext &k = *keys[l]->p;
+            if (k.batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (!v.empty() && k.slots != v[0]->slots)
+                throw std::invalid_argument(which + " has " + std::to_string(k.slots) + " slots, key 0 " +
+                                            std::to_string(v[0]->slots));
+            if (!v.empty() && k.level != v[0]->level)
+                throw std::invalid_argument(which + " sits at level " + std::to_string(k.level) + ", key 0 at level " +
+                                            std::to_string(v[0]->level) + ": the keys' levels differ");
+            v.push_back(&k);
+        }
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.cache_masks = ctx->mask_cache;
+        ds.tiebreak = ctx->sort_tiebreak;
+        ds.shard_rank = 0;  // unsharded, like the select and the group sums
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        // the depth refusal (a context too shallow) is raised by the operator before it starts any work
+        *rank = wrap(ds.lexRank(v, eps, SignFunc::CompositeSign, cfgof(n, dg, df)));
+    });
+}
+int fhe_lex_rank_levels(int key_level, int nkeys, int n, int dg, int df, int *rank_level) {
+    return guard([&] {
+        const LexRankLevels lv = lexRankLevels(key_level, nkeys, n, dg, df);
+        if (rank_level) *rank_level = lv.rank_level;
+    });
+}
+int fhe_sub_lex_stacked(fhe_ctx *ctx, const fhe_ct *const *as, int nkeys, const fhe_ct *const *bs, int count,
+                        const fhe_pt *const *ps, double eps, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(as);
+        NEED(bs);
+        NEED(out);
+        if (nkeys < 2 || nkeys > 4) throw std::invalid_argument("fhe_sub_lex_stacked: nkeys must lie in 2..4");
+        if (count < 1) throw std::invalid_argument("fhe_sub_lex_stacked: count must be >= 1");
+        std::vector<const Ciphertext *> a, b;
+        std::vector<const Plaintext *> p;
+        for (int l = 0; l < nkeys; ++l) {
+            NEED(as[l]);
+            a.push_back(as[l]->p.get());
+        }
+        for (int i = 0; i < nkeys * count; ++i) {
+            NEED(bs[i]);
+            b.push_back(bs[i]->p.get());
+        }
+        if (ps)
+            for (int i = 0; i < count; ++i) {
+                NEED(ps[i]);
+                p.push_back(ps[i]->p.get());
+            }
+        *out = wrap(ctx->eng->sub_lex_stacked(a, b, p, eps));
+    });
+}
+int fhe_mul_lex(fhe_ctx *ctx, const fhe_ct *t, double t_const, const fhe_ct *u, const fhe_ct *w, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(t);
+        NEED(u);
+        NEED(w);
+        NEED(out);
+        *out = wrap(ctx->eng->mul_lex(*t->p, t_const, *u->p, *w->p));
+    });
+}
 int fhe_pt_encode_select(fhe_ctx *ctx, const int32_t *targets, int ntargets, int member, int num_slots, int N,
                          int level_c, int level_k, fhe_pt **out) {
     if (out) out[0] = out[1] = nullptr;

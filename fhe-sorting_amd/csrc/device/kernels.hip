@@ -1513,6 +1513,119 @@ __global__ __launch_bounds__(NT) void k_tensor_pairs(u64 *d01, u64 *d2, const u6
     }
 }
 
+// The differences of a chunk of comparator batches under L lexicographic keys
+// (lexRank), all written straight into one stack of
+// (2 L - 1) `count` members.  With d = a_key - b_{key, i}: a leading key writes
+// member (2 key) count + i = d with Kp 2^shp (+eps) added to c0 and member
+// (2 key + 1) count + i = d with Kn 2^shn (-eps) added to c0, both from one load of
+// b; the last key writes member 2 (L - 1) count + i = d, with p_i added to c0 when
+// the tie-break offsets are given.  a_key's two pairs of words are loaded once per
+// tile of SLX_TM operands (B = the launch's operands per key): a leading key moves
+// 6 B + 2 ceil(B / TM) limb-units against the 14 B of sub_stacked and two
+// add_consts, the last key k_sub_add_plain_stacked's 5 B + 2 ceil(B / TM) (4 B
+// without offsets).  sub_mod, then add_mod of the constant's residue or of the
+// plaintext: the words of k_sub and k_c0_op (modes 0 and 1).  A last tile narrower
+// than SLX_TM repeats its last operand and stores only the valid ones.
+// grid: x = coefficient block, y = limb, z = key * tiles + tile.
+constexpr int SLX_TM = 4;
+constexpr int SLX_KEYS = 4;
+struct SubLexArgs {
+    const u64 *a[SLX_KEYS];
+    const u64 *b[LIN_MAX];      // key-major: b[key * B + i]
+    const u64 *p[LIN_MAX / 2];  // the last key's offsets (B of them) when has_p
+    int L, B, has_p;
+};
+__global__ __launch_bounds__(NT) void k_sub_lex_stacked(u64 *out, SubLexArgs A, size_t count, int64_t Kp, int shp,
+                                                        int64_t Kn, int shn, size_t ln_all, const Mod *mods, int logN) {
+    constexpr int TM = SLX_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int tiles = (A.B + TM - 1) / TM;
+    const int key = (int)(blockIdx.z / (unsigned)tiles), m0 = (int)(blockIdx.z % (unsigned)tiles) * TM;  // block-uniform
+    const u64 *ap = A.a[key];
+    const ulonglong2 a0 = ld2(ap + lo), a1 = ld2(ap + ln_all + lo);
+    ulonglong2 b0[TM], b1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const u64 *bp = A.b[key * A.B + min(m0 + t, A.B - 1)];
+        b0[t] = ld2(bp + lo);
+        b1[t] = ld2(bp + ln_all + lo);
+    }
+    if (key < A.L - 1) {  // a leading key: d + eps and d - eps
+        const u64 wp = smod(Kp, shp, mods[l]), wn = smod(Kn, shn, mods[l]);
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < A.B) {
+                const u64 d0x = sub_mod(a0.x, b0[t].x, q), d0y = sub_mod(a0.y, b0[t].y, q);
+                const ulonglong2 d1 = make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q));
+                u64 *o = out + ((size_t)(2 * key) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, make_ulonglong2(add_mod(d0x, wp, q), add_mod(d0y, wp, q)));
+                st2(o + ln_all, d1);
+                u64 *om = o + count * 2 * ln_all;
+                st2(om, make_ulonglong2(add_mod(d0x, wn, q), add_mod(d0y, wn, q)));
+                st2(om + ln_all, d1);
+            }
+    } else {  // the last key: d, with the tie-break offset when one is given
+        ulonglong2 p[TM];
+        if (A.has_p) {
+#pragma unroll
+            for (int t = 0; t < TM; ++t) p[t] = ld2(A.p[min(m0 + t, A.B - 1)] + lo);
+        }
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < A.B) {
+                ulonglong2 d0 = make_ulonglong2(sub_mod(a0.x, b0[t].x, q), sub_mod(a0.y, b0[t].y, q));
+                if (A.has_p) d0 = make_ulonglong2(add_mod(d0.x, p[t].x, q), add_mod(d0.y, p[t].y, q));
+                u64 *o = out + ((size_t)(2 * key) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, d0);
+                st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
+            }
+    }
+}
+
+// k_tensor_c's left constant with the right operand formed on load (lexRank's
+// Horner step): member z's left operand is t_z with C.aK 2^ash
+// added to c0 (add_const's words; 0 adds nothing), its right operand u_z - w_z
+// (k_sub's sub_mod on both polynomials), so neither t + c nor u - w is written to
+// memory: 9 limb-units per member against the 6 + 4 + 9 of sub, add_const and
+// k_tensor.  t, u and w are stacks of one level, members at stride sa.
+__global__ __launch_bounds__(NT) void k_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w,
+                                                   size_t ln_all, size_t sa, int64_t aK, int ash, const Mod *mods,
+                                                   int logN) {
+    __shared__ u64 wc;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const Mod m = mods[l];
+    if (threadIdx.x == 0) wc = smod(aK, ash, m);
+    __syncthreads();
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const size_t z = blockIdx.z, o = (size_t)l * n + k;
+    const u64 *T = t + z * sa, *U = u + z * sa, *W = w + z * sa;
+    ulonglong2 a0 = ld2(T + o);
+    const ulonglong2 a1 = ld2(T + ln_all + o);
+    const ulonglong2 u0 = ld2(U + o), u1 = ld2(U + ln_all + o);
+    const ulonglong2 w0 = ld2(W + o), w1 = ld2(W + ln_all + o);
+    const u64 wa = wc;
+    a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
+    const ulonglong2 b0 = make_ulonglong2(sub_mod(u0.x, w0.x, m.q), sub_mod(u0.y, w0.y, m.q));
+    const ulonglong2 b1 = make_ulonglong2(sub_mod(u1.x, w1.x, m.q), sub_mod(u1.y, w1.y, m.q));
+    ulonglong2 e0, e1, e2;
+    e0.x = mul_barrett(a0.x, b0.x, m);
+    e0.y = mul_barrett(a0.y, b0.y, m);
+    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
+    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
+    e2.x = mul_barrett(a1.x, b1.x, m);
+    e2.y = mul_barrett(a1.y, b1.y, m);
+    st2(d01 + z * 2 * ln_all + o, e0);
+    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
+    st2(d2 + z * ln_all + o, e2);
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3377,6 +3490,43 @@ void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *
         launch_clocked(inst_name<TC_PC>("k_tensor_pairs"), B, k_tensor_pairs<TC_PC>, ew_grid(logN, limbs, members * groups),
                        dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, a2, b + mo * 2 * ln_all, ln_all, sa, Pn,
                        members, mods, logN);
+    }
+}
+int sub_lex_tile() { return SLX_TM; }
+void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *const *bs, const u64 *const *ps, int count,
+                        int64_t Kp, int shp, int64_t Kn, int shn, int limbs, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || count <= 0) return;
+    if (keys < 1 || keys > SLX_KEYS) throw std::invalid_argument("ew_sub_lex_stacked: unsupported key count");
+    const size_t ln_all = (size_t)limbs << logN;
+    // operands of one launch: keys * B pointers in b, B in p
+    const int per_launch = std::min(LIN_MAX / keys, LIN_MAX / 2);
+    for (int base = 0; base < count; base += per_launch) {
+        SubLexArgs A{};
+        A.L = keys;
+        A.B = std::min(per_launch, count - base);
+        A.has_p = ps != nullptr;
+        for (int l = 0; l < keys; ++l) {
+            A.a[l] = as[l];
+            for (int i = 0; i < A.B; ++i) A.b[l * A.B + i] = bs[(size_t)l * count + base + i];
+        }
+        if (ps)
+            for (int i = 0; i < A.B; ++i) A.p[i] = ps[base + i];
+        const int tiles = (A.B + SLX_TM - 1) / SLX_TM;
+        const double B = 8.0 * ((keys - 1) * (6.0 * A.B + 2.0 * tiles) + (ps ? 5.0 : 4.0) * A.B + 2.0 * tiles) * ln_all;
+        launch_clocked("k_sub_lex_stacked", B, k_sub_lex_stacked, ew_grid(logN, limbs, keys * tiles), dim3(NT), st,
+                       out + (size_t)base * 2 * ln_all, A, (size_t)count, Kp, shp, Kn, shn, ln_all, mods, logN);
+    }
+}
+void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, int limbs, int members, size_t sa,
+                   int64_t aK, int ash, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < members; base += 65535) {  // grid z limit
+        const int cnt = std::min(65535, members - base);
+        const double B = 8.0 * 9.0 * cnt * ln_all;
+        launch_clocked("k_tensor_lex", B, k_tensor_lex, ew_grid(logN, limbs, cnt), dim3(NT), st,
+                       d01 + (size_t)base * 2 * ln_all, d2 + (size_t)base * ln_all, t + (size_t)base * sa,
+                       u + (size_t)base * sa, w + (size_t)base * sa, ln_all, sa, aK, ash, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

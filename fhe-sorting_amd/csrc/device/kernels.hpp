@@ -288,6 +288,22 @@ void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int m
 int tensor_pairs_per_thread();
 void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
                      size_t sa, const Mod *mods, int logN, hipStream_t st);
+// The stacked differences of `keys` lexicographic keys (as[key]: [2][limbs][n];
+// bs key-major, bs[key * count + i]; ps: `count` plaintexts [limbs][n] or nullptr)
+// in one pass: with d = as[key] - bs[key * count + i], member (2 key) count + i of
+// out = d with Kp 2^shp added to c0 and member (2 key + 1) count + i = d with
+// Kn 2^shn added to c0 for key < keys - 1; member 2 (keys - 1) count + i = d of the
+// last key with ps[i] added to c0.  A thread applies a key's words to up to
+// sub_lex_tile() operands and loads each b once; word for word ew_sub, then
+// ew_c0_op mode 0 / mode 1, per member.  keys <= 4.
+int sub_lex_tile();
+void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *const *bs, const u64 *const *ps, int count,
+                        int64_t Kp, int shp, int64_t Kn, int shn, int limbs, const Mod *mods, int logN, hipStream_t st);
+// ew_tensor of the stacks t, u, w (`members` members at stride sa, one level):
+// member z of d01 / d2 holds the tensor of (t[z] with aK 2^ash added to c0,
+// u[z] - w[z]), word for word ew_c0_op mode 0, ew_sub and ew_tensor.
+void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, int limbs, int members, size_t sa,
+                   int64_t aK, int ash, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);

@@ -2633,6 +2633,114 @@ CtPtr Engine::sub_pm_const_stacked(const Ciphertext &a0, const std::vector<const
     count_bytes(6.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
+// FHE_LEX_FUSED (A/B, default 1): the one-pass kernels of sub_lex_stacked and mul_lex
+static bool lex_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_LEX_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+CtPtr Engine::sub_lex_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
+                              const std::vector<const Plaintext *> &ps, double eps) {
+    const int L = (int)as.size();
+    if (L < 2 || L > 4) throw std::invalid_argument("sub_lex_stacked: 2 to 4 keys");
+    if (bs.empty() || bs.size() % (size_t)L) throw std::invalid_argument("sub_lex_stacked: one operand list per key");
+    const int B = (int)(bs.size() / (size_t)L);
+    if (!ps.empty() && (int)ps.size() != B) throw std::invalid_argument("sub_lex_stacked: one plaintext per operand");
+    for (auto *a : as)
+        if (!a || a->batch != 1 || a->level != as[0]->level || a->limbs != as[0]->limbs)
+            throw std::invalid_argument("sub_lex_stacked: the keys must be single ciphertexts at one level");
+    for (auto *b : bs)
+        if (!b || b->batch != 1 || b->level != bs[0]->level)
+            throw std::invalid_argument("sub_lex_stacked: operands differ in level");
+    // the plaintexts meet the differences, which sit at the deeper of the two levels
+    const int level = std::max(as[0]->level, bs[0]->level);
+    for (auto *p : ps)
+        if (!p || p->level != level) throw std::invalid_argument("sub_lex_stacked: level mismatch");
+    const bool above = as[0]->level > bs[0]->level;  // every b would be adjusted: per-member ops, as sub_stacked
+    if (above || !lex_fused_enabled()) {
+        std::vector<CtPtr> keep;
+        std::vector<const Ciphertext *> v;
+        for (int l = 0; l < L; ++l) {
+            const std::vector<const Ciphertext *> bl(bs.begin() + (size_t)l * B, bs.begin() + (size_t)(l + 1) * B);
+            if (above) {
+                std::vector<CtPtr> d;
+                for (auto *b : bl) d.push_back(sub(*as[l], *b));
+                if (l < L - 1) {
+                    for (auto &x : d) keep.push_back(add_const(*x, eps));
+                    for (auto &x : d) keep.push_back(add_const(*x, -eps));
+                } else {
+                    for (int i = 0; i < B; ++i) keep.push_back(ps.empty() ? d[i] : add_plain(*d[i], *ps[i]));
+                }
+            } else if (l < L - 1) {  // the plain form (A/B): the stacked differences, then the two sides on the stack
+                CtPtr d = sub_stacked(*as[l], bl);
+                keep.push_back(add_const(*d, eps));
+                keep.push_back(add_const(*d, -eps));
+            } else {
+                keep.push_back(ps.empty() ? sub_stacked(*as[l], bl) : sub_add_plain_stacked(*as[l], bl, ps));
+            }
+        }
+        for (auto &x : keep) v.push_back(x.get());
+        return stack(v);
+    }
+    std::vector<CtPtr> adj;  // sub(a, b) adjusts a the same way
+    std::vector<const u64 *> ap, bp, pp;
+    for (auto *a : as) {
+        if (a->level < level) {
+            adj.push_back(level_adjust(*a, level));
+            a = adj.back().get();
+        }
+        ap.push_back(a->data);
+    }
+    const Ciphertext &a0 = adj.empty() ? *as[0] : *adj[0];
+    const size_t ell = a0.limbs;
+    for (auto *b : bs) {
+        if (b->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_lex_stacked: operand limb count differs from its level's");
+        bp.push_back(b->data);
+    }
+    for (auto *p : ps) {
+        if (p->limbs != ell) throw std::invalid_argument("sub_lex_stacked: plaintext limb count differs from its level's");
+        pp.push_back(p->data);
+    }
+    auto r = new_ct(a0.level, a0.slots, a0.scale, ell, (2 * L - 1) * B);
+    const host::SConst Kp = host::const_at_scale(eps, a0.scale), Kn = host::const_at_scale(-eps, a0.scale);
+    dev::ew_sub_lex_stacked(r->data, ap.data(), L, bp.data(), pp.empty() ? nullptr : pp.data(), B, Kp.k, Kp.sh, Kn.k,
+                            Kn.sh, (int)ell, MODS, LOGN, ST);
+    const int tile = dev::sub_lex_tile();
+    const double tiles = (double)((B + tile - 1) / tile);
+    count_bytes((L - 1) * (6.0 * ell * B + 2.0 * ell * tiles) + (pp.empty() ? 4.0 : 5.0) * ell * B + 2.0 * ell * tiles, 1);
+    return r;
+}
+CtPtr Engine::mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, const Ciphertext &w) {
+    auto &I = *impl;
+    if (u.batch < 1 || w.batch != u.batch || t.batch != u.batch)
+        throw std::invalid_argument("mul_lex: t, u and w differ in member count");
+    if (w.level != u.level || w.limbs != u.limbs) throw std::invalid_argument("mul_lex: u and w differ in level");
+    if (!lex_fused_enabled())  // the plain form (A/B): every step an op of its own
+        return mul(t_const != 0.0 ? *add_const(t, t_const) : t, *sub(u, w));
+    if (t.level != u.level || t.limbs != u.limbs)  // mul level-adjusts an operand: u - w first, then the product
+        return mul_add(t, *sub(u, w), {}, {}, nullptr, nullptr, t_const, 0.0);
+    if (t.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    const int B = t.batch;
+    ctr.hmult += B;
+    ctr.keyswitch += B;
+    ctr.rescale += B;
+    const size_t nn = n(), ell = t.limbs;
+    // the product, the sub it replaces and, with a constant, add_const's copy
+    count_bytes(6.0 * ell + ks_units(ell) + 6.0 * ell + (t_const != 0.0 ? 4.0 * ell : 0.0), B);
+    auto d01m = I.alloc((size_t)B * 2 * ell * nn * 8), d2m = I.alloc((size_t)B * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    const host::SConst Ka = t_const != 0.0 ? host::const_at_scale(t_const, t.scale) : host::SConst{};
+    dev::ew_tensor_lex(d01, d2, t.data, u.data, w.data, (int)ell, B, 2 * ell * nn, Ka.k, Ka.sh, MODS, LOGN, ST);
+    const bool fuse = I.ks_fuse(B);
+    auto extm = I.modup(d2, ell, B, ell * nn, fuse);
+    auto r = new_ct(t.level + 1, t.slots, I.P.delta[t.level + 1], ell - 1, B);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
+    return r;
+}
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {
     if (ps.empty()) throw std::invalid_argument("sub_plain_stacked: no plaintexts");
     if (a.batch != 1) throw std::invalid_argument("sub_plain_stacked: a must be one ciphertext");

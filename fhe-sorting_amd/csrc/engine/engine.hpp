@@ -336,6 +336,27 @@ class Engine {
     // rules.  FHE_GROUP_FUSED=0 (A/B): sub_stacked, then negate / add_const on
     // the stack, stacked.
     CtPtr sub_pm_const_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs, double c);
+    // The differences of lexicographic keys (DirectSortN::lexRank):
+    // with L = as.size() keys (2..4), count = bs.size() / L and bs key-major
+    // (bs[l count + i]), the result is a stack of (2 L - 1) count members: for a
+    // leading key l < L - 1, member (2 l) count + i = add_const(sub(*as[l], b), eps)
+    // and member (2 l + 1) count + i = add_const(sub(*as[l], b), -eps); for the last
+    // key, member 2 (L - 1) count + i = sub(*as[L - 1], b), with add_plain(., *ps[i])
+    // when ps is not empty; word for word, written by one launch
+    // (k_sub_lex_stacked: each b loaded once, a key's words once per tile).  The
+    // as share a level and so do the bs; sub_stacked's level rules: as at a lower
+    // level are level-adjusted once, at a higher one every member takes its own
+    // ops; the ps sit at the differences' level.  FHE_LEX_FUSED=0 (A/B):
+    // sub_stacked and add_const per key, stacked.
+    CtPtr sub_lex_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
+                          const std::vector<const Plaintext *> &ps, double eps);
+    // member z = mul(add_const(member(t, z), t_const), sub(member(u, z), member(w, z)))
+    // word for word for the B-member stacks t, u, w (u and w at one level).  With t
+    // at that level too, one tensor pass (k_tensor_lex) adds the constant to c0 as
+    // it loads t and forms u - w as it loads them, then mul's relinearisation /
+    // rescale tail; with t at another level (mul would level-adjust an operand) or
+    // under FHE_LEX_FUSED=0 it is sub, then the product.
+    CtPtr mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, const Ciphertext &w);
     CtPtr sum_members(const Ciphertext &a);
     // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
     // consecutive members, in one launch (k_sum_member_groups); an empty acc

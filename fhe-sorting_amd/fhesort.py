@@ -150,6 +150,12 @@ _SIGS = {
     'fhe_sub_pm_const_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_double,
                                            C.POINTER(C.c_void_p)]),
     'fhe_mul_pairs': (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_direct_lex_rank': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.c_double, C.c_int, ip, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_lex_rank_levels': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]),
+    'fhe_sub_lex_stacked': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int,
+                                      C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p)]),
+    'fhe_mul_lex': (C.c_int, [vp, vp, C.c_double, vp, vp, C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -901,6 +907,57 @@ class Context:
         mul(add(member(a, z), member(a_add, z)), member(b_stack, p * B + z)) word for word"""
         return self._new(lib().fhe_mul_pairs, a.h, a_add.h, b_stack.h, ncols)
 
+    def lex_rank(self, keys, eps, N, rots, cfg):
+        """Lexicographic rank (fhe_direct_lex_rank): slot e holds the position of row
+        e among the N rows ordered by keys[0], then keys[1], ... (2 to 4 single
+        ciphertexts at one level, most significant first) -- ORDER BY a, b, or one
+        wide key split into digits.  With set_sort_tiebreak set it is the stable
+        lexicographic argsort rank; without it rows tied on every key share their
+        ranks as the plain rank's ties do.  Values equal on a leading key must agree
+        far below eps, distinct ones differ by >= 2 eps, |difference| + eps <= 1, and
+        the sign configuration must resolve eps; 0 < eps < 0.5.  The rank ends at
+        lex_rank_levels(...) and feeds direct_sort(mode=2), direct_sort_columns and
+        direct_select as any rank does."""
+        r = np.asarray(rots, dtype=np.int32)
+        keys = list(keys)
+        arr = (C.c_void_p * max(1, len(keys)))(*[None if k is None else k.h for k in keys])
+        out = C.c_void_p()
+        _chk(lib().fhe_direct_lex_rank(self.h, arr, len(keys), float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2],
+                                       C.byref(out)))
+        return Ct(self, out.value)
+
+    def lex_sort_columns(self, keys, cols, eps, N, rots, cfg):
+        """Records ordered by several encrypted keys: lex_rank(keys), then
+        direct_sort_columns(rank=...) of cols.  Pass keys among cols to get them
+        sorted too.  The context needs the sort's depth plus len(keys) - 1."""
+        return self.direct_sort_columns(None, cols, N, rots, cfg, rank=self.lex_rank(keys, eps, N, rots, cfg))
+
+    @staticmethod
+    def lex_rank_levels(key_level, nkeys, cfg):
+        return lex_rank_levels(key_level, nkeys, cfg)
+
+    def sub_lex_stacked(self, as_, bs, eps, ps=None):
+        """fhe_sub_lex_stacked: with L = len(as_) keys and bs key-major (L * count
+        ciphertexts), the stack of (2 L - 1) * count members: for a leading key l,
+        member 2 l count + i is add_const(sub(as_[l], bs[l count + i]), eps) and member
+        (2 l + 1) count + i the same with -eps; for the last key, member
+        2 (L - 1) count + i is sub(as_[L - 1], bs[...]) [add_plain ps[i]]; word for word"""
+        L = len(as_)
+        if L == 0 or len(bs) % L:
+            raise ValueError('sub_lex_stacked: one operand list per key')
+        count = len(bs) // L
+        if ps is not None and len(ps) != count:
+            raise ValueError('sub_lex_stacked: one plaintext per operand')
+        aa = (C.c_void_p * max(1, L))(*[a.h for a in as_])
+        ba = (C.c_void_p * max(1, len(bs)))(*[b.h for b in bs])
+        pa = None if ps is None else (C.c_void_p * max(1, count))(*[p.h for p in ps])
+        return self._new(lib().fhe_sub_lex_stacked, aa, L, ba, count, pa, float(eps))
+
+    def mul_lex(self, t, t_const, u, w):
+        """member z = mul(add_const(member(t, z), t_const), sub(member(u, z), member(w, z)))
+        word for word, in one tensor pass where t, u and w share a level"""
+        return self._new(lib().fhe_mul_lex, t.h, float(t_const), u.h, w.h)
+
     def mul_columns(self, a, cols):
         """the stack a (B members) times each single ciphertext of cols: member
         p * B + z of the result is mul(member(a, z), cols[p]) word for word"""
@@ -1165,6 +1222,16 @@ def group_sum_levels(key_level, cfg):
     if rc != FHE_OK:
         raise FheError(rc, lib().fhe_last_error().decode())
     return col.value, out.value
+
+
+def lex_rank_levels(key_level, nkeys, cfg):
+    """fhe_lex_rank_levels (pure host): the level lex_rank's result ends at for nkeys
+    keys at key_level under the composite sign cfg = (n, dg, df)"""
+    out = C.c_int()
+    rc = lib().fhe_lex_rank_levels(int(key_level), int(nkeys), cfg[0], cfg[1], cfg[2], C.byref(out))
+    if rc != FHE_OK:
+        raise FheError(rc, lib().fhe_last_error().decode())
+    return out.value
 
 
 def select_layout(N, num_slots, ntargets):

@@ -440,6 +440,69 @@ int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const 
 int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_ct *b_stack, int ncols,
                   fhe_ct **out_stack);
 
+/* Lexicographic rank: order rows by several encrypted key columns (the project's
+ * own extension, like fhe_direct_select and fhe_direct_group_sum).
+ * keys[0] .. keys[nkeys - 1], most significant first, 2 <= nkeys <= 4, each a single
+ * ciphertext of N rows in N slots, all at one level k.  *rank holds at slot e the
+ * position of row e among the rows ordered by keys[0], then keys[1], ...: ORDER BY
+ * a, b -- or one key wider than the sign resolves, split into digits.  It is an
+ * ordinary rank ciphertext and feeds fhe_direct_sort mode 2, fhe_direct_sort_columns
+ * and fhe_direct_select (rank != NULL) unchanged.
+ * Per pair (e, j) with d_l = keys[l]_e - keys[l]_j:  u_l = sign(d_l + eps) and
+ * w_l = sign(d_l - eps) on the leading keys (two signs per leading key, none taken
+ * at 0), s = sign(d_last + E) on the last key, E the fhe_set_sort_tiebreak offset
+ * when one is set;  T_last = s + 1,  T_l = (u_l - w_l) T_{l+1} + 2^(nkeys-1-l) (w_l + 1),
+ * rank_e = 2^-nkeys sum_j T_0 - c.  With the tie-break set c = 1 and the rank is the
+ * stable lexicographic argsort rank; without it c = 1/2 and rows tied on every key
+ * share their ranks as the plain rank's ties do (tests/tie_model.py).
+ * The caller guarantees, as for the group sums:
+ *   - values equal on a leading key are equal up to noise far below eps,
+ *   - distinct ones differ by at least 2 eps,
+ *   - |d_l| + eps <= 1, the sign's domain,
+ *   - the sign configuration (n, dg, df) resolves eps,
+ *   - the tie-break's own conditions hold on the last key,
+ * and 0 < eps < 0.5.  Levels (fhe_lex_rank_levels): with the sign consuming D
+ * levels every sign output sits at L_m = k + 1 + D and the rank ends at
+ * rank_level = L_m + nkeys, nkeys - 1 levels below where fhe_direct_sort mode 1
+ * ends: a context for the lexicographic rank and the index check needs the depth
+ * of fhe_size_parameters(N) plus nkeys - 1.  rots are the sort's rotation keys.
+ * The batches run stacked in chunks of fhe_set_sort_stack / (2 nkeys - 1) on
+ * fhe_set_sort_lanes lanes; the result depends on neither, nor on
+ * fhe_set_mask_cache (0: the call re-encodes at its start what it caches).
+ * Unsharded: a sharded caller has no use for it yet (the rank it feeds to a
+ * sharded index check is computed once and passed in).
+ * FHE_EINVAL (the message names the key at fault) for nkeys outside 2..4, a null
+ * key, a key that is a stack, slot counts or levels that differ, and eps outside
+ * (0, 0.5); FHE_EDEPTH, before any work, for a context without rank_level levels.
+ * On failure *rank is NULL. */
+int fhe_direct_lex_rank(fhe_ctx *ctx, const fhe_ct *const *keys, int nkeys, double eps, int N, const int32_t *rots,
+                        int nrot, int n, int dg, int df, fhe_ct **rank);
+/* pure host: rank_level above for nkeys keys at key_level under the composite sign
+ * (n, dg, df), n = 3 or 4.  The pointer may be NULL.  FHE_EINVAL for nkeys outside
+ * 2..4, a negative level or degree, or another n. */
+int fhe_lex_rank_levels(int key_level, int nkeys, int n, int dg, int df, int *rank_level);
+/* for tests and bindings: the differences of nkeys keys against count shifted
+ * copies each (bs key-major: bs[l count + i]) as one stack of (2 nkeys - 1) count
+ * members.  For a leading key l, member (2 l) count + i = fhe_add_const(fhe_sub(as[l],
+ * bs[l count + i]), +eps) and member (2 l + 1) count + i the same with -eps; for the
+ * last key, member 2 (nkeys - 1) count + i = fhe_sub(as[nkeys - 1], bs[..]), with
+ * fhe_add_plain(., ps[i]) when ps is not NULL (count plaintexts at the differences'
+ * level); word for word, written by one kernel that loads every b once and a key
+ * once per four operands (FHE_LEX_FUSED=0, read once per process: the stacked
+ * differences and add_const per key).  The as share a level and so do the bs; as at
+ * a lower level are level-adjusted once, at a higher one every member takes its
+ * own operations.  FHE_EINVAL for counts or levels that do not fit. */
+int fhe_sub_lex_stacked(fhe_ctx *ctx, const fhe_ct *const *as, int nkeys, const fhe_ct *const *bs, int count,
+                        const fhe_pt *const *ps /* may be NULL */, double eps, fhe_ct **out);
+/* and the Horner step they feed: t, u and w are stacks of B members, u and w at one
+ * level; member z of the result = fhe_mul_relin(fhe_add_const(t_z, t_const),
+ * fhe_sub(u_z, w_z)) word for word.  With t at the level of u and w it is one tensor
+ * pass that adds the constant to c0 as it loads t and forms u - w as it loads them,
+ * then the product's relinearisation and rescale; with t at another level, or under
+ * FHE_LEX_FUSED=0, the difference is formed first and the product follows.
+ * FHE_EINVAL for member counts or levels of u and w that do not fit. */
+int fhe_mul_lex(fhe_ctx *ctx, const fhe_ct *t, double t_const, const fhe_ct *u, const fhe_ct *w, fhe_ct **out);
+
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
  * grows with it).  Results do not depend on it. */
