@@ -1434,7 +1434,7 @@ CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConf
     // tie-breaking: the offsets E_b of this rank's batches, at the level the
     // differences sit at (one masked sum's rescale below x)
     std::map<int, PtPtr> offs;
-    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0]->level + 1);
+    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0]->level + 1, tiebreak);
     cc.sync();  // baby steps, dup and the offsets are read by every lane
     const size_t chunk = (size_t)std::max(1, max_stack);
     auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
@@ -1481,11 +1481,12 @@ CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConf
 // E_b of the given batches from the cache; the missing ones are encoded in one
 // device batch on the main engine.  cache_masks false: all of them are encoded
 // again (the select's rule for its own plaintexts).
-std::map<int, PtPtr> DirectSortN::tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level) {
+std::map<int, PtPtr> DirectSortN::tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level,
+                                                  double eps) {
     std::map<int, PtPtr> out;
     std::vector<int> missing;
     for (int b : batches) {
-        auto it = tiebreak_cache.find(std::make_tuple(num_slots, b, level, tiebreak));
+        auto it = tiebreak_cache.find(std::make_tuple(num_slots, b, level, eps));
         if (it != tiebreak_cache.end() && cache_masks)
             out[b] = it->second;
         else
@@ -1497,9 +1498,9 @@ std::map<int, PtPtr> DirectSortN::tiebreakOffsets(int num_slots, const std::vect
         for (auto &e : lane_eng) e->sync();  // nothing of the last rank still reads the old ones
     }
     if (tiebreak_cache.size() + missing.size() > 1024) tiebreak_cache.clear();
-    auto pts = cc.encode_tiebreak(missing, num_slots, N, tiebreak, level);  // synchronises the main stream
+    auto pts = cc.encode_tiebreak(missing, num_slots, N, eps, level);  // synchronises the main stream
     for (size_t i = 0; i < missing.size(); ++i) {
-        tiebreak_cache.insert_or_assign(std::make_tuple(num_slots, missing[i], level, tiebreak), pts[i]);
+        tiebreak_cache.insert_or_assign(std::make_tuple(num_slots, missing[i], level, eps), pts[i]);
         out[missing[i]] = pts[i];
     }
     return out;
@@ -2013,6 +2014,170 @@ std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext
     return outs;
 }
 
+// Running sums.  groupSums' layout with the rank's own predicate: slot s of batch b
+// holds kl[s mod N] - kr[(s mod N + t) mod N] (+ the mode's offset), t = b P_ + s / N,
+// and the equally shifted column beside it.  The indicator is s + 1 (2 or 0) for
+// the one-sided modes and u - w (2 or 0) for RunBetween; the 1/2 rides on the
+// columns' level adjustment as in groupSums.  The count halves every batch's
+// indicator on its own (constructRank's compare), so that in RunRows it is the
+// tie-broken rank + 1 word for word.
+std::vector<CtPtr> DirectSortN::runningSums(const Ciphertext &kl, const Ciphertext *lo, const Ciphertext &kr,
+                                            const std::vector<const Ciphertext *> &cols, int mode, double eps,
+                                            bool want_count, SignFunc f, const SignConfig &cfg) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)cols.size();
+    if (mode < RunRows || mode > RunBetween)
+        throw std::invalid_argument("running sum: mode must lie in 0..3, got " + std::to_string(mode));
+    if (mode == RunBetween && !lo) throw std::invalid_argument("running sum: the between mode needs the lower bound");
+    if (mode != RunBetween && lo) throw std::invalid_argument("running sum: a lower bound is given outside the between mode");
+    if (P == 0 && !want_count) throw std::invalid_argument("running sum: neither a column nor the count is asked for");
+    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("running sum: eps must lie in (0, 0.5)");
+    if (kl.batch != 1 || kr.batch != 1) throw std::invalid_argument("running sum: a key is a stack");
+    if (kl.slots != kr.slots) throw std::invalid_argument("running sum: the keys differ in slot count");
+    if (kl.level != kr.level)
+        throw std::invalid_argument("running sum: the keys sit at different levels (" + std::to_string(kl.level) + ", " +
+                                    std::to_string(kr.level) + ")");
+    if (lo) {
+        if (lo->batch != 1) throw std::invalid_argument("running sum: the lower bound is a stack");
+        if (lo->slots != kl.slots) throw std::invalid_argument("running sum: the lower bound differs in slot count");
+        if (lo->level != kl.level || lo->limbs != kl.limbs)
+            throw std::invalid_argument("running sum: the lower bound sits at another level (" +
+                                        std::to_string(lo->level) + ", the keys at " + std::to_string(kl.level) + ")");
+    }
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("running sum: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument("running sum: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->slots != kl.slots)
+            throw std::invalid_argument("running sum: column " + std::to_string(p) + " has " +
+                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(kl.slots));
+    }
+    const GroupSumLevels lv =
+        groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
+    if (lv.out_level > cc.params().L)
+        throw std::runtime_error("running sum: keys at level " + std::to_string(kl.level) + " need " +
+                                 std::to_string(lv.out_level) + " levels, the context has " +
+                                 std::to_string(cc.params().L) + ": no levels left");
+    for (int p = 0; p < P; ++p)
+        if (cols[p]->level > lv.col_max_level)
+            throw std::runtime_error("running sum: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
+                                     std::to_string(lv.col_max_level) + "): no levels left to meet the indicator");
+    if (!cache_masks) refresh_masks();
+    std::optional<AlgoPhase> ph;
+    ph.emplace("run_baby");
+    std::vector<CtPtr> kbaby = babySteps(kr, s.np);
+    for (auto &b : kbaby) b->slots = s.num_slots;
+    // the columns, prepared as groupSums prepares them (the same cached masks serve both)
+    std::vector<std::vector<CtPtr>> cbaby(P);
+    for (int p = 0; p < P; ++p) {
+        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 0.5, lv.match_level - 1), s.np);
+        for (auto &b : cbaby[p]) b->slots = s.num_slots;
+    }
+    ph.reset();
+    std::vector<int> mine(s.num_batch);
+    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
+    CtPtr dup = cc.clone(kl), dup_lo;
+    dup->slots = s.num_slots;
+    if (lo) {
+        dup_lo = cc.clone(*lo);
+        dup_lo->slots = s.num_slots;
+    }
+    // RunRows: the offsets E_b of this call's eps, at the level the differences sit at
+    std::map<int, PtPtr> offs;
+    if (mode == RunRows) offs = tiebreakOffsets(s.num_slots, mine, lv.diff_level, eps);
+    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
+    const int per_batch = mode == RunBetween ? 2 : 1;  // sign members per batch
+    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / per_batch);
+    // columns per stacked product, as rotationIndexCheckColumns bounds them
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
+    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
+    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level match_level + 1)
+    std::mutex cnt_mu;
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph("run_batches");
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        CtPtr cnt;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr sg;
+            {
+                std::vector<CtPtr> shifted = vecRotsOptMany(L, kbaby, s.num_partition, s.num_slots, s.np, iss);
+                std::vector<const Ciphertext *> ptrs;
+                for (auto &x : shifted) ptrs.push_back(x.get());
+                CtPtr d;
+                if (mode == RunRows) {  // d_b + E_b, the rank's own tie-broken differences
+                    std::vector<const Plaintext *> es;
+                    for (int b : iss) es.push_back(offs.at(b).get());
+                    d = E.sub_add_plain_stacked(*dup, ptrs, es);
+                } else if (mode == RunBetween) {  // hi - s_b + eps (members 0 .. B - 1), lo - s_b - eps (B .. 2 B - 1)
+                    d = E.sub_bounds_stacked({dup.get(), dup_lo.get()}, ptrs, {eps, -eps});
+                } else {
+                    d = E.sub_bounds_stacked({dup.get()}, ptrs, {mode == RunLE ? eps : -eps});
+                }
+                shifted.clear();
+                sg = sign(*d, E, f, cfg);
+            }
+            if (sg->level != lv.match_level) throw std::logic_error("running sum: unexpected sign output level");
+            Ciphertext up = *sg, dn = *sg;  // RunBetween: views of the two halves
+            up.batch = dn.batch = B;
+            if (mode == RunBetween) dn.data = sg->data + (size_t)B * 2 * sg->limbs * E.n();
+            if (want_count) {  // the indicator is written out only here
+                CtPtr a = mode == RunBetween ? E.sub(up, dn) : E.add_const(up, 1.0);
+                CtPtr c = E.mul_const(*a, 0.5);
+                E.add_inplace(cnt, B == 1 ? *c : *E.sum_members(*c));
+            }
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
+                for (int p = p0; p < p0 + Pg; ++p)
+                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
+                CtPtr prod = mode == RunBetween ? E.mul_pairs_sub(up, dn, *asStack(E, sv), Pg)
+                                                : E.mul_pairs_const(up, 1.0, *asStack(E, sv), Pg);
+                sv.clear();
+                E.sum_member_groups(*prod, Pg, accs[g]);
+            }
+        }
+        if (cnt) {
+            std::lock_guard<std::mutex> lk(cnt_mu);
+            cnt_parts.push_back(cnt);
+        }
+        if (bs.empty() || P == 0) return nullptr;
+        if (accs.size() == 1) return accs[0];
+        std::vector<const Ciphertext *> all;
+        for (auto &a : accs) all.push_back(a.get());
+        return E.stack(all);  // the column groups, in column order
+    });
+    CtPtr out, cnt;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(out, *p);
+    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    cnt_parts.clear();
+    AlgoPhase fold_ph("run_fold");
+    auto fold = [&](CtPtr &v) {
+        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    };
+    std::vector<CtPtr> outs;
+    if (P > 0) {
+        fold(out);
+        for (int p = 0; p < P; ++p) {
+            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
+            outs.back()->slots = N;
+        }
+    }
+    if (want_count) {
+        fold(cnt);
+        outs.push_back(cnt);
+        outs.back()->slots = N;
+    }
+    return outs;
+}
+
 LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split) {
     if (nkeys < 2 || nkeys > 4) throw std::invalid_argument("lex rank: 2 to 4 keys, got " + std::to_string(nkeys));
     const GroupSumLevels g = groupSumLevels(key_level, n, dg, df, ps_split);  // the same differences and sign
@@ -2067,7 +2232,7 @@ CtPtr DirectSortN::lexRank(const std::vector<const Ciphertext *> &keys, double e
     for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
     // the last key's tie-break offsets, at the level the differences sit at
     std::map<int, PtPtr> offs;
-    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0][0]->level + 1);
+    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0][0]->level + 1, tiebreak);
     cc.sync();  // the baby steps, the dups and the offsets are read by every lane
     // a chunk's sign runs over (2 L - 1) members per batch: the plain rank's footprint
     const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / (2 * L - 1));

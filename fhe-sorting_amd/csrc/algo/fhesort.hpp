@@ -320,6 +320,36 @@ class DirectSortN {
     // Unsharded.  The result feeds rotationIndexCheckN / rotationIndexCheckColumns /
     // selectColumns as any rank does.
     CtPtr lexRank(const std::vector<const Ciphertext *> &keys, double eps, SignFunc f, const SignConfig &cfg);
+    // Running sums (the project's own extension): with P = cols.size(),
+    // out[p] holds at slot e  sum_j c_ej cols[p]_j, j over the N rows of the right
+    // table; want_count appends sum_j c_ej as out[P].  The weight c_ej by mode:
+    //   RunRows     (sign(kl_e - kr_j + E_ej) + 1) / 2, E the tie-break offset of §6.3 built
+    //               from this call's eps (+eps where j <= e): the stable row order, ROWS
+    //               UNBOUNDED PRECEDING with the row itself;
+    //   RunLE       (sign(kl_e - kr_j + eps) + 1) / 2: kr_j <= kl_e, peers included (SQL's
+    //               default RANGE frame, searchsorted side = right);
+    //   RunLT       (sign(kl_e - kr_j - eps) + 1) / 2: kr_j < kl_e (searchsorted side = left);
+    //   RunBetween  (sign(kl_e - kr_j + eps) - sign(lo_e - kr_j - eps)) / 2 with kl the upper
+    //               bound: lo_e <= kr_j <= hi_e, both ends closed (the band join, the RANGE
+    //               BETWEEN window).  lo is required in this mode and refused in the others.
+    // groupSums' layout, levels (groupSumLevels), column preparation (halved on the
+    // way to L_m - 1, sharing its cached masks), chunking, lanes and column groups.
+    // A chunk of B batches is one sign over a B stack (2 B for RunBetween:
+    // Engine::sub_bounds_stacked, or sub_add_plain_stacked for RunRows); the
+    // indicator s + 1 (u - w) is formed as the stacked product loads it
+    // (Engine::mul_pairs_const / mul_pairs_sub) and written out only for the count,
+    // which is halved per batch as constructRank's compare is: in RunRows with
+    // kr = kl, add_const(count, -1) is the tie-broken rank word for word.  Needs
+    // equal keys equal far below eps, distinct keys (bounds included) >= 2 eps
+    // apart, every sign argument within [-1, 1], a sign configuration that
+    // resolves eps, and lo <= hi.  A column above col_max_level or a context
+    // without out_level levels is refused before any work.  The words do not
+    // depend on max_stack, lanes, max_col_members or cache_masks.  Unsharded;
+    // `tiebreak` has no effect.
+    enum RunMode { RunRows = 0, RunLE = 1, RunLT = 2, RunBetween = 3 };
+    std::vector<CtPtr> runningSums(const Ciphertext &kl, const Ciphertext *lo, const Ciphertext &kr,
+                                   const std::vector<const Ciphertext *> &cols, int mode, double eps, bool want_count,
+                                   SignFunc f, const SignConfig &cfg);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;
@@ -396,7 +426,8 @@ class DirectSortN {
     std::map<std::tuple<std::vector<int>, int, int, int>, std::array<PtPtr, 2>> select_cache;
     // the tie-break offsets E_b per (num_slots, batch, level, eps)
     std::map<std::tuple<int, int, int, double>, PtPtr> tiebreak_cache;
-    std::map<int, PtPtr> tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level);
+    // of the given batches for the offset eps (the rank passes `tiebreak`, the running sums their own)
+    std::map<int, PtPtr> tiebreakOffsets(int num_slots, const std::vector<int> &batches, int level, double eps);
     std::vector<int> rot_indices;
     std::vector<std::unique_ptr<Engine>> lane_eng;
     std::vector<std::unique_ptr<RotationComposerN>> lane_rot;

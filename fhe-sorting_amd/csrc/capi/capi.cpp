@@ -811,6 +811,119 @@ int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_
         *out_stack = wrap(ctx->eng->mul_pairs(*a->p, *a_add->p, *b_stack->p, ncols));
     });
 }
+int fhe_direct_running_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *left_lo, const fhe_ct *right_key,
+                           const fhe_ct *const *cols, int ncols, int mode, double eps, int N, const int32_t *rots,
+                           int nrot, int n, int dg, int df, fhe_ct **outs, fhe_ct **count_out) {
+    if (outs)
+        for (int p = 0; p < ncols; ++p) outs[p] = nullptr;
+    if (count_out) *count_out = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        if (!left_key || !left_key->p) throw std::invalid_argument("fhe_direct_running_sum: the left key is null");
+        if (!right_key || !right_key->p) throw std::invalid_argument("fhe_direct_running_sum: the right key is null");
+        if (mode < FHE_RUN_ROWS || mode > FHE_RUN_BETWEEN)
+            throw std::invalid_argument("fhe_direct_running_sum: mode must lie in 0..3, got " + std::to_string(mode));
+        if (mode == FHE_RUN_BETWEEN && (!left_lo || !left_lo->p))
+            throw std::invalid_argument("fhe_direct_running_sum: FHE_RUN_BETWEEN needs left_lo, the lower bound");
+        if (mode != FHE_RUN_BETWEEN && left_lo)
+            throw std::invalid_argument("fhe_direct_running_sum: left_lo is given outside FHE_RUN_BETWEEN");
+        if (ncols < 0) throw std::invalid_argument("fhe_direct_running_sum: ncols must be >= 0");
+        if (ncols == 0 && !count_out)
+            throw std::invalid_argument("fhe_direct_running_sum: neither a column nor the count is asked for");
+        if (ncols > 0 && (!cols || !outs))
+            throw std::invalid_argument("fhe_direct_running_sum: null column or output array");
+        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_running_sum: eps must lie in (0, 0.5)");
+        const Ciphertext &kl = *left_key->p, &kr = *right_key->p;
+        if (kl.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: the left key is a stack");
+        if (kr.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: the right key is a stack");
+        if (kr.slots != kl.slots)
+            throw std::invalid_argument("fhe_direct_running_sum: the right key has " + std::to_string(kr.slots) +
+                                        " slots, the left key " + std::to_string(kl.slots));
+        if (kr.level != kl.level)
+            throw std::invalid_argument("fhe_direct_running_sum: the keys sit at different levels (" +
+                                        std::to_string(kl.level) + ", " + std::to_string(kr.level) + ")");
+        if (left_lo) {
+            const Ciphertext &lo = *left_lo->p;
+            if (lo.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: left_lo is a stack");
+            if (lo.slots != kl.slots)
+                throw std::invalid_argument("fhe_direct_running_sum: left_lo has " + std::to_string(lo.slots) +
+                                            " slots, the left key " + std::to_string(kl.slots));
+            if (lo.level != kl.level)
+                throw std::invalid_argument("fhe_direct_running_sum: left_lo sits at level " + std::to_string(lo.level) +
+                                            ", the left key at " + std::to_string(kl.level));
+        }
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            const std::string which = "fhe_direct_running_sum: column " + std::to_string(p);
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
+            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (cols[p]->p->slots != kl.slots)
+                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the keys " +
+                                            std::to_string(kl.slots));
+            v.push_back(cols[p]->p.get());
+        }
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = 0;  // unsharded, like the group sums
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        // the depth refusals (a column too deep, a context too shallow) are raised
+        // by the operator before it starts any work
+        std::vector<CtPtr> r = ds.runningSums(kl, left_lo ? left_lo->p.get() : nullptr, kr, v, mode, eps,
+                                              count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
+        if (count_out) *count_out = wrap(r[(size_t)ncols]);
+    });
+}
+int fhe_sub_bounds_stacked(fhe_ctx *ctx, const fhe_ct *const *as, int nbounds, const fhe_ct *const *bs, int count,
+                           const double *consts, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(as);
+        NEED(bs);
+        NEED(consts);
+        NEED(out);
+        if (nbounds < 1 || nbounds > 2) throw std::invalid_argument("fhe_sub_bounds_stacked: nbounds must be 1 or 2");
+        if (count < 1) throw std::invalid_argument("fhe_sub_bounds_stacked: count must be >= 1");
+        std::vector<const Ciphertext *> a, b;
+        for (int i = 0; i < nbounds; ++i) {
+            NEED(as[i]);
+            a.push_back(as[i]->p.get());
+        }
+        for (int i = 0; i < count; ++i) {
+            NEED(bs[i]);
+            b.push_back(bs[i]->p.get());
+        }
+        *out = wrap(ctx->eng->sub_bounds_stacked(a, b, std::vector<double>(consts, consts + nbounds)));
+    });
+}
+int fhe_mul_pairs_const(fhe_ctx *ctx, const fhe_ct *a, double c, const fhe_ct *b_stack, int ncols,
+                        fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(b_stack);
+        NEED(out_stack);
+        *out_stack = wrap(ctx->eng->mul_pairs_const(*a->p, c, *b_stack->p, ncols));
+    });
+}
+int fhe_mul_pairs_sub(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_sub, const fhe_ct *b_stack, int ncols,
+                      fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(a_sub);
+        NEED(b_stack);
+        NEED(out_stack);
+        *out_stack = wrap(ctx->eng->mul_pairs_sub(*a->p, *a_sub->p, *b_stack->p, ncols));
+    });
+}
 int fhe_direct_lex_rank(fhe_ctx *ctx, const fhe_ct *const *keys, int nkeys, double eps, int N, const int32_t *rots,
                         int nrot, int n, int dg, int df, fhe_ct **rank) {
     if (rank) *rank = nullptr;

@@ -1626,6 +1626,128 @@ __global__ __launch_bounds__(NT) void k_tensor_lex(u64 *d01, u64 *d2, const u64 
     st2(d2 + z * ln_all + o, e2);
 }
 
+// The bounded differences of a chunk of comparator batches (runningSums,
+// DESIGN.md §6.6): for each of the NB left operands ("bounds") a_v and every b_i,
+// member v `count` + i of out = a_v - b_i with K_v 2^sh_v added to c0, written
+// straight into the stack.  Each b_i is loaded once for all bounds and every
+// a_v's two pairs of words once per tile of SBD_TM members:
+// (2 + 2 NB) B + 2 NB ceil(B / TM) limb-units against the 10 NB B of one sub and
+// one add_const per member and bound.  sub_mod, then add_mod of the constant's
+// residue: the words of k_sub and k_c0_op (mode 0).  A last tile narrower than
+// SBD_TM repeats its last member and stores only the valid ones.
+// grid: x = coefficient block, y = limb, z = member tile.
+constexpr int SBD_TM = 4;
+constexpr int SBD_NB = 2;
+struct SubBoundsArgs {
+    const u64 *a[SBD_NB];
+    const u64 *b[LIN_MAX];
+    int64_t K[SBD_NB];
+    int sh[SBD_NB];
+    int B;
+};
+template <int NB>
+__global__ __launch_bounds__(NT) void k_sub_bounds_stacked(u64 *out, SubBoundsArgs A, size_t count, size_t ln_all,
+                                                           const Mod *mods, int logN) {
+    constexpr int TM = SBD_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int m0 = blockIdx.z * TM;
+    ulonglong2 a0[NB], a1[NB];
+#pragma unroll
+    for (int v = 0; v < NB; ++v) {
+        a0[v] = ld2(A.a[v] + lo);
+        a1[v] = ld2(A.a[v] + ln_all + lo);
+    }
+    ulonglong2 b0[TM], b1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const int m = min(m0 + t, A.B - 1);  // block-uniform
+        b0[t] = ld2(A.b[m] + lo);
+        b1[t] = ld2(A.b[m] + ln_all + lo);
+    }
+    u64 w[NB];
+#pragma unroll
+    for (int v = 0; v < NB; ++v) w[v] = smod(A.K[v], A.sh[v], mods[l]);
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+        if (m0 + t < A.B) {
+#pragma unroll
+            for (int v = 0; v < NB; ++v) {
+                u64 *o = out + ((size_t)v * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, make_ulonglong2(add_mod(sub_mod(a0[v].x, b0[t].x, q), w[v], q),
+                                       add_mod(sub_mod(a0[v].y, b0[t].y, q), w[v], q)));
+                st2(o + ln_all, make_ulonglong2(sub_mod(a1[v].x, b1[t].x, q), sub_mod(a1[v].y, b1[t].y, q)));
+            }
+        }
+}
+
+// k_tensor_pairs with the left operand of the running sums formed on load
+// (runningSums).  MODE 0: member z's left operand is s_z with
+// K 2^sh added to c0 (add_const's words); MODE 1: u_z - w_z on both polynomials
+// (k_sub's words), so neither the indicator s + 1 nor u - w is written to memory.
+// s (u) and w are stacks of `members` members at stride sa, b a column-major
+// stack of P * members members: grid z = group * members + z; a thread forms
+// member z's left operand once and the tensor against the up to PC columns of
+// its group, member p * members + z of b, every column's loads issued ahead of
+// the arithmetic.  Output member p * members + z, the words k_tensor gives on
+// (the left operand, b[p * members + z]).  The last group is guarded.
+template <int PC, int MODE>
+__global__ __launch_bounds__(NT) void k_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b,
+                                                   size_t ln_all, size_t sa, int64_t K, int sh, int P, int members,
+                                                   const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod m = mods[l];
+    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
+    const size_t o = (size_t)l * n + k;
+    const u64 *A = a + (size_t)z * sa;
+    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
+    ulonglong2 c0 = make_ulonglong2(0, 0), c1 = make_ulonglong2(0, 0);
+    if (MODE == 1) {
+        const u64 *W = w + (size_t)z * sa;
+        c0 = ld2(W + o);
+        c1 = ld2(W + ln_all + o);
+    }
+    ulonglong2 b0[PC], b1[PC];
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < P) {
+            const u64 *Bp = b + ((size_t)(p0 + j) * members + z) * 2 * ln_all;
+            b0[j] = ld2(Bp + o);
+            b1[j] = ld2(Bp + ln_all + o);
+        }
+    }
+    if (MODE == 0) {
+        const u64 wc = smod(K, sh, m);
+        a0 = make_ulonglong2(add_mod(a0.x, wc, m.q), add_mod(a0.y, wc, m.q));
+    } else {
+        a0 = make_ulonglong2(sub_mod(a0.x, c0.x, m.q), sub_mod(a0.y, c0.y, m.q));
+        a1 = make_ulonglong2(sub_mod(a1.x, c1.x, m.q), sub_mod(a1.y, c1.y, m.q));
+    }
+#pragma unroll
+    for (int j = 0; j < PC; ++j) {
+        if (p0 + j < P) {
+            ulonglong2 e0, e1, e2;
+            e0.x = mul_barrett(a0.x, b0[j].x, m);
+            e0.y = mul_barrett(a0.y, b0[j].y, m);
+            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
+            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
+            e2.x = mul_barrett(a1.x, b1[j].x, m);
+            e2.y = mul_barrett(a1.y, b1[j].y, m);
+            const size_t mo = (size_t)(p0 + j) * members + z;
+            st2(d01 + mo * 2 * ln_all + o, e0);
+            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
+            st2(d2 + mo * ln_all + o, e2);
+        }
+    }
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3527,6 +3649,52 @@ void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, 
         launch_clocked("k_tensor_lex", B, k_tensor_lex, ew_grid(logN, limbs, cnt), dim3(NT), st,
                        d01 + (size_t)base * 2 * ln_all, d2 + (size_t)base * ln_all, t + (size_t)base * sa,
                        u + (size_t)base * sa, w + (size_t)base * sa, ln_all, sa, aK, ash, mods, logN);
+    }
+}
+int sub_bounds_tile() { return SBD_TM; }
+void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64 *const *bs, int count,
+                           const int64_t *Ks, const int *shs, int limbs, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || count <= 0) return;
+    if (bounds < 1 || bounds > SBD_NB) throw std::invalid_argument("ew_sub_bounds_stacked: unsupported bound count");
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < count; base += LIN_MAX) {
+        SubBoundsArgs A{};
+        A.B = std::min(LIN_MAX, count - base);
+        for (int v = 0; v < bounds; ++v) {
+            A.a[v] = as[v];
+            A.K[v] = Ks[v];
+            A.sh[v] = shs[v];
+        }
+        for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
+        const int tiles = (A.B + SBD_TM - 1) / SBD_TM;
+        const double B = 8.0 * ((2.0 + 2.0 * bounds) * A.B + 2.0 * bounds * tiles) * ln_all;
+        u64 *o = out + (size_t)base * 2 * ln_all;
+        if (bounds == 1)
+            launch_clocked(inst_name<1>("k_sub_bounds_stacked"), B, k_sub_bounds_stacked<1>, ew_grid(logN, limbs, tiles),
+                           dim3(NT), st, o, A, (size_t)count, ln_all, mods, logN);
+        else
+            launch_clocked(inst_name<2>("k_sub_bounds_stacked"), B, k_sub_bounds_stacked<2>, ew_grid(logN, limbs, tiles),
+                           dim3(NT), st, o, A, (size_t)count, ln_all, mods, logN);
+    }
+}
+void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, int P, int limbs, int members,
+                   size_t sa, int64_t K, int sh, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0 || P <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    // grid z = members * groups stays below the 65535 limit: whole column groups per launch
+    const int per_launch = std::max(1, 65535 / members / TC_PC) * TC_PC;
+    for (int base = 0; base < P; base += per_launch) {
+        const int Pn = std::min(per_launch, P - base), groups = (Pn + TC_PC - 1) / TC_PC;
+        const double B = 8.0 * ((w ? 4.0 : 2.0) * members * groups + 5.0 * Pn * members) * ln_all;
+        const size_t mo = (size_t)base * members;  // first column member of this launch
+        if (w)
+            launch_clocked(inst_name<TC_PC, 1>("k_tensor_run"), B, k_tensor_run<TC_PC, 1>,
+                           ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all,
+                           a, w, b + mo * 2 * ln_all, ln_all, sa, K, sh, Pn, members, mods, logN);
+        else
+            launch_clocked(inst_name<TC_PC, 0>("k_tensor_run"), B, k_tensor_run<TC_PC, 0>,
+                           ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all,
+                           a, w, b + mo * 2 * ln_all, ln_all, sa, K, sh, Pn, members, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

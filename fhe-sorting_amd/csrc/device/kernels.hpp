@@ -304,6 +304,21 @@ void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *con
 // u[z] - w[z]), word for word ew_c0_op mode 0, ew_sub and ew_tensor.
 void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, int limbs, int members, size_t sa,
                    int64_t aK, int ash, const Mod *mods, int logN, hipStream_t st);
+// The bounded differences of `bounds` (1 or 2) left operands as[v] against the bs
+// (all [2][limbs][n]) in one pass: member v count + i of out ([bounds count][2][limbs][n])
+// = as[v] - bs[i] with Ks[v] 2^shs[v] added to c0.  A thread loads each bs[i] once
+// for all bounds and applies the as' words to up to sub_bounds_tile() members; word
+// for word ew_sub, then ew_c0_op mode 0, per member and bound.
+int sub_bounds_tile();
+void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64 *const *bs, int count,
+                           const int64_t *Ks, const int *shs, int limbs, const Mod *mods, int logN, hipStream_t st);
+// ew_tensor_pairs with the left operand formed on load: member p * members + z of
+// d01 / d2 holds the tensor of (left_z, b[p * members + z]) with left_z = a[z] with
+// K 2^sh added to c0 when w is null (ew_c0_op mode 0's words), a[z] - w[z] otherwise
+// (ew_sub's words); a and w are stacks of `members` members at stride sa.  The left
+// operand is formed once per tensor_pairs_per_thread() columns.
+void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, int P, int limbs, int members,
+                   size_t sa, int64_t K, int sh, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);

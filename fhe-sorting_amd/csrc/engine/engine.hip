@@ -2741,6 +2741,126 @@ CtPtr Engine::mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, 
     I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
     return r;
 }
+// FHE_RUN_FUSED (A/B, default 1): the one-pass kernels of sub_bounds_stacked and mul_pairs_const / mul_pairs_sub
+static bool run_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_RUN_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+CtPtr Engine::sub_bounds_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
+                                 const std::vector<double> &consts) {
+    const int V = (int)as.size();
+    if (V < 1 || V > 2) throw std::invalid_argument("sub_bounds_stacked: 1 or 2 left operands");
+    if ((int)consts.size() != V) throw std::invalid_argument("sub_bounds_stacked: one constant per left operand");
+    if (bs.empty()) throw std::invalid_argument("sub_bounds_stacked: no operands");
+    for (auto *a : as)
+        if (!a || a->batch != 1 || a->level != as[0]->level || a->limbs != as[0]->limbs || a->slots != as[0]->slots)
+            throw std::invalid_argument("sub_bounds_stacked: the left operands must be single ciphertexts at one level");
+    for (auto *b : bs)
+        if (!b || b->level != bs[0]->level || b->batch != 1)
+            throw std::invalid_argument("sub_bounds_stacked: operands differ in level");
+    const int B = (int)bs.size();
+    const bool above = as[0]->level > bs[0]->level;  // every b would be adjusted: per-member ops, as sub_stacked
+    if (above || !run_fused_enabled()) {
+        std::vector<CtPtr> keep;
+        std::vector<const Ciphertext *> v;
+        for (int k = 0; k < V; ++k) {
+            if (above) {
+                for (auto *b : bs) keep.push_back(add_const(*sub(*as[k], *b), consts[k]));
+            } else {  // the plain form (A/B): the stacked differences, then the constant on the stack in place
+                CtPtr d = sub_stacked(*as[k], bs);
+                add_const_inplace(d, consts[k]);
+                keep.push_back(d);
+            }
+        }
+        if (keep.size() == 1) return keep[0];
+        for (auto &x : keep) v.push_back(x.get());
+        return stack(v);
+    }
+    const int level = bs[0]->level;
+    std::vector<CtPtr> adj;  // sub(a, b) adjusts a the same way
+    std::vector<const u64 *> ap, bp;
+    for (auto *a : as) {
+        if (a->level < level) {
+            adj.push_back(level_adjust(*a, level));
+            a = adj.back().get();
+        }
+        ap.push_back(a->data);
+    }
+    const Ciphertext &a0 = adj.empty() ? *as[0] : *adj[0];
+    const size_t ell = a0.limbs;
+    for (auto *b : bs) {
+        if (b->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_bounds_stacked: operand limb count differs from its level's");
+        bp.push_back(b->data);
+    }
+    auto r = new_ct(a0.level, a0.slots, a0.scale, ell, V * B);
+    int64_t Ks[2] = {0, 0};
+    int shs[2] = {0, 0};
+    for (int k = 0; k < V; ++k) {
+        const host::SConst K = host::const_at_scale(consts[k], a0.scale);
+        Ks[k] = K.k;
+        shs[k] = K.sh;
+    }
+    dev::ew_sub_bounds_stacked(r->data, ap.data(), V, bp.data(), B, Ks, shs, (int)ell, MODS, LOGN, ST);
+    const int tile = dev::sub_bounds_tile();
+    count_bytes((2.0 + 2.0 * V) * ell * B + 2.0 * V * ell * ((B + tile - 1) / tile), 1);
+    return r;
+}
+CtPtr Engine::mul_pairs_const(const Ciphertext &a, double c, const Ciphertext &b, int Pn) {
+    return mul_pairs_left("mul_pairs_const", a, nullptr, c, b, Pn);
+}
+CtPtr Engine::mul_pairs_sub(const Ciphertext &a, const Ciphertext &a_sub, const Ciphertext &b, int Pn) {
+    return mul_pairs_left("mul_pairs_sub", a, &a_sub, 0.0, b, Pn);
+}
+CtPtr Engine::mul_pairs_left(const char *what, const Ciphertext &a, const Ciphertext *w, double c, const Ciphertext &b,
+                             int Pn) {
+    auto &I = *impl;
+    const std::string me(what);
+    if (Pn < 1) throw std::invalid_argument(me + ": no columns");
+    if (a.batch < 1) throw std::invalid_argument(me + ": a holds no member");
+    if (w && w->batch != a.batch) throw std::invalid_argument(me + ": a and a_sub differ in member count");
+    if (w && (w->level != a.level || w->limbs != a.limbs)) throw std::invalid_argument(me + ": a and a_sub differ in level");
+    if ((long long)b.batch != (long long)Pn * a.batch)
+        throw std::invalid_argument(me + ": b holds " + std::to_string(b.batch) + " members, need " + std::to_string(Pn) +
+                                    " columns of " + std::to_string(a.batch));
+    if (b.level != a.level || b.limbs != a.limbs) throw std::invalid_argument(me + ": b is not at a's level");
+    const int B = a.batch, PB = Pn * B;
+    const size_t nn = n(), ell = a.limbs;
+    if (!run_fused_enabled()) {  // the plain form (A/B): the left operand written out, then one mul per column, stacked
+        CtPtr left = w ? sub(a, *w) : add_const(a, c);
+        std::vector<CtPtr> prod;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < Pn; ++p) {
+            Ciphertext col = b;
+            col.data = b.data + (size_t)p * B * 2 * ell * nn;
+            col.batch = B;
+            prod.push_back(mul(*left, col));
+            v.push_back(prod.back().get());
+        }
+        return prod.size() == 1 ? prod[0] : stack(v);
+    }
+    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    ctr.hmult += PB;
+    ctr.keyswitch += PB;
+    ctr.rescale += PB;
+    count_bytes(5.0 * ell + ks_units(ell), PB);
+    const int per = dev::tensor_pairs_per_thread();
+    count_bytes((w ? 4.0 : 2.0) * ell * ((Pn + per - 1) / per), B);
+    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    const host::SConst K = w ? host::SConst{} : host::const_at_scale(c, a.scale);
+    dev::ew_tensor_run(d01, d2, a.data, w ? w->data : nullptr, b.data, Pn, (int)ell, B, 2 * ell * nn, K.k, K.sh, MODS,
+                       LOGN, ST);
+    const bool fuse = I.ks_fuse(PB);
+    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
+    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
+    return r;
+}
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {
     if (ps.empty()) throw std::invalid_argument("sub_plain_stacked: no plaintexts");
     if (a.batch != 1) throw std::invalid_argument("sub_plain_stacked: a must be one ciphertext");

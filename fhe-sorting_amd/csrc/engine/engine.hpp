@@ -357,6 +357,30 @@ class Engine {
     // rescale tail; with t at another level (mul would level-adjust an operand) or
     // under FHE_LEX_FUSED=0 it is sub, then the product.
     CtPtr mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, const Ciphertext &w);
+    // The bounded differences of the running sums (DirectSortN::runningSums,
+    // DESIGN.md §6.6): with V = as.size() left operands (1 or 2, single ciphertexts
+    // at one level), one constant each and B = bs.size(), member v B + i =
+    // add_const(sub(*as[v], *bs[i]), consts[v]) word for word, written straight into
+    // the V B stack by one launch (k_sub_bounds_stacked: each bs[i] loaded once for
+    // all bounds, the as' words once per tile of members).  sub_stacked's level
+    // rules: as at a lower level than the bs are level-adjusted once, at a higher
+    // one every member takes its own ops.  FHE_RUN_FUSED=0 (A/B): sub_stacked per
+    // bound, then add_const in place.
+    CtPtr sub_bounds_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
+                             const std::vector<double> &consts);
+    // the B-member stack a against the column-major stack b of P B members, all at
+    // one level: member p B + z of the result is mul(add_const(member(a, z), c),
+    // member(b, p B + z)) (mul_pairs_const) or mul(sub(member(a, z), member(a_sub, z)),
+    // member(b, p B + z)) (mul_pairs_sub) word for word.  One tensor pass
+    // (k_tensor_run: the left operand formed once per thread for up to four
+    // columns, never written to memory), then mul's relinearisation / rescale
+    // tail on P B members.  FHE_RUN_FUSED=0 (A/B): the left operand formed by
+    // add_const / sub, then one mul per column, stacked.
+    CtPtr mul_pairs_const(const Ciphertext &a, double c, const Ciphertext &b, int P);
+    CtPtr mul_pairs_sub(const Ciphertext &a, const Ciphertext &a_sub, const Ciphertext &b, int P);
+    // the two above: a_sub null takes the constant
+    CtPtr mul_pairs_left(const char *what, const Ciphertext &a, const Ciphertext *a_sub, double c, const Ciphertext &b,
+                         int P);
     CtPtr sum_members(const Ciphertext &a);
     // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
     // consecutive members, in one launch (k_sum_member_groups); an empty acc

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('FHE_LIB') or os.path.join(HERE, 'lib', 'libfhesort.so
 COEFF_DIR = os.path.join(HERE, 'data')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'fhe_gpu.h')
 PS_SPLIT_ENGINE, PS_SPLIT_OPENFHE = 0, 1  # fhe_set_ps_split (include/fhe_gpu.h)
+RUN_ROWS, RUN_LE, RUN_LT, RUN_BETWEEN = range(4)  # fhe_direct_running_sum's modes (FHE_RUN_*)
 
 FHE_OK, FHE_EINVAL, FHE_ENOKEY, FHE_EDEPTH, FHE_EHIP, FHE_ENOMEM, FHE_EINTERNAL, FHE_ENOCOMM, FHE_EIO = range(9)
 NAF, BNAF, BINARY = 0, 1, 2
@@ -150,6 +151,13 @@ _SIGS = {
     'fhe_sub_pm_const_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_double,
                                            C.POINTER(C.c_void_p)]),
     'fhe_mul_pairs': (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_direct_running_sum': (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_int,
+                                         ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_void_p)]),
+    'fhe_sub_bounds_stacked': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, dp,
+                                         C.POINTER(C.c_void_p)]),
+    'fhe_mul_pairs_const': (C.c_int, [vp, vp, C.c_double, vp, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_mul_pairs_sub': (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_direct_lex_rank': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.c_double, C.c_int, ip, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_lex_rank_levels': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]),
@@ -906,6 +914,53 @@ class Context:
         ncols * B members: member p * B + z of the result is
         mul(add(member(a, z), member(a_add, z)), member(b_stack, p * B + z)) word for word"""
         return self._new(lib().fhe_mul_pairs, a.h, a_add.h, b_stack.h, ncols)
+
+    def running_sum(self, left_key, right_key, cols, eps, N, rots, cfg, mode=RUN_ROWS, lo=None, count=False):
+        """Running sums (fhe_direct_running_sum): out[p] has N slots, slot e holds the
+        sum of cols[p] over the right rows j that the mode selects for left row e:
+        RUN_ROWS the rows up to and including e in the stable key order (right_key =
+        left_key: SUM(v) OVER (ORDER BY key ROWS UNBOUNDED PRECEDING)), RUN_LE
+        right_key_j <= left_key_e (the default RANGE frame, the range lookup,
+        searchsorted side='right' with the count), RUN_LT right_key_j < left_key_e
+        (side='left'), RUN_BETWEEN lo_e <= right_key_j <= left_key_e with left_key the
+        upper bound and lo required (the band join, the sliding RANGE window).
+        count=True: returns (outs, count), the count holding the number of selected
+        right rows; with RUN_ROWS and right_key = left_key, count - 1 is the stable
+        rank.  Equal keys must agree far below eps, distinct keys and bounds differ
+        by >= 2 eps, every difference +- eps lie in [-1, 1], and the sign
+        configuration must resolve eps; 0 < eps < 0.5.  Levels are group_sum_levels'."""
+        r = np.asarray(rots, dtype=np.int32)
+        cols = list(cols)
+        arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
+        outs = (C.c_void_p * max(1, len(cols)))()
+        cnt = C.c_void_p()
+        _chk(lib().fhe_direct_running_sum(self.h, None if left_key is None else left_key.h,
+                                          None if lo is None else lo.h,
+                                          None if right_key is None else right_key.h, arr, len(cols), int(mode),
+                                          float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
+                                          C.byref(cnt) if count else None))
+        res = [Ct(self, outs[i]) for i in range(len(cols))]
+        return (res, Ct(self, cnt.value)) if count else res
+
+    def sub_bounds_stacked(self, as_, bs, consts):
+        """stack of len(as_) len(bs) members (1 or 2 left operands): member v len(bs) + i
+        is add_const(sub(as_[v], bs[i]), consts[v]) word for word, in one pass"""
+        if len(as_) != len(consts):
+            raise ValueError('sub_bounds_stacked: one constant per left operand')
+        aa = (C.c_void_p * max(1, len(as_)))(*[a.h for a in as_])
+        ba = (C.c_void_p * max(1, len(bs)))(*[b.h for b in bs])
+        cs = np.ascontiguousarray(consts, dtype=np.float64).reshape(-1)
+        return self._new(lib().fhe_sub_bounds_stacked, aa, len(as_), ba, len(bs), _dbl(cs))
+
+    def mul_pairs_const(self, a, c, b_stack, ncols):
+        """the B-member stack a against the column-major stack b_stack of ncols * B
+        members: member p * B + z of the result is
+        mul(add_const(member(a, z), c), member(b_stack, p * B + z)) word for word"""
+        return self._new(lib().fhe_mul_pairs_const, a.h, float(c), b_stack.h, ncols)
+
+    def mul_pairs_sub(self, a, a_sub, b_stack, ncols):
+        """as mul_pairs_const with the left operand sub(member(a, z), member(a_sub, z))"""
+        return self._new(lib().fhe_mul_pairs_sub, a.h, a_sub.h, b_stack.h, ncols)
 
     def lex_rank(self, keys, eps, N, rots, cfg):
         """Lexicographic rank (fhe_direct_lex_rank): slot e holds the position of row

@@ -440,6 +440,76 @@ int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const 
 int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_ct *b_stack, int ncols,
                   fhe_ct **out_stack);
 
+/* Running sums: add up columns over the right rows whose key is smaller than, or
+ * within a range of, the left row's (the project's own extension, like
+ * fhe_direct_select and fhe_direct_group_sum).  left_key,
+ * right_key, left_lo and every column hold N rows in N slots.  outs[p] has N
+ * slots; slot e holds
+ *     sum_j c_ej cols[p]_j,   j = 0 .. N - 1,
+ * and *count_out (optional) sum_j c_ej.  The weight c_ej of a pair by mode, with
+ * kl = left_key, kr = right_key:
+ *   FHE_RUN_ROWS     (sign(kl_e - kr_j + E_ej) + 1) / 2, E the tie-break offset of
+ *                    fhe_set_sort_tiebreak built from this call's eps (+eps where
+ *                    j <= e, -eps where j > e): with right_key = left_key the rows
+ *                    before row e in the stable order and the row itself, SUM(v)
+ *                    OVER (ORDER BY key ROWS UNBOUNDED PRECEDING);
+ *   FHE_RUN_LE       (sign(kl_e - kr_j + eps) + 1) / 2: kr_j <= kl_e, peers included --
+ *                    SQL's default RANGE frame, SELECT SUM(b.v) FROM b WHERE b.k <= a.k
+ *                    per row of a, and with the count searchsorted(side = right);
+ *   FHE_RUN_LT       (sign(kl_e - kr_j - eps) + 1) / 2: kr_j < kl_e, searchsorted(side =
+ *                    left);
+ *   FHE_RUN_BETWEEN  (sign(hi_e - kr_j + eps) - sign(lo_e - kr_j - eps)) / 2 with hi =
+ *                    left_key and lo = left_lo: lo_e <= kr_j <= hi_e, both ends closed --
+ *                    the band join and RANGE BETWEEN w PRECEDING AND w FOLLOWING.
+ * left_lo is required for FHE_RUN_BETWEEN and must be NULL otherwise.  Open ends
+ * and descending order are the caller's fhe_add_const / fhe_negate on the keys.
+ * The caller guarantees: 0 < eps < 0.5; equal keys agree far below eps; distinct
+ * keys, bounds included, differ by at least 2 eps; every sign argument has
+ * magnitude <= 1; the sign configuration (n, dg, df) resolves eps; lo_e <= hi_e.
+ * The count is halved batch by batch as the rank's compare is, so in FHE_RUN_ROWS
+ * with right_key = left_key fhe_add_const(count, -1) is word for word the rank of
+ * fhe_direct_sort mode 1 under fhe_set_sort_tiebreak(eps).  Levels are
+ * fhe_group_sum_levels': a column may sit at col_max_level at most and every
+ * output ends at out_level.  The batches run stacked in chunks of
+ * fhe_set_sort_stack on fhe_set_sort_lanes lanes, the columns in groups bounded by
+ * fhe_set_sort_column_members; the result does not depend on any of them, nor on
+ * fhe_set_mask_cache (0: the call re-encodes the cached masks at its start).
+ * Unsharded.  fhe_set_sort_tiebreak has no effect here.  FHE_RUN_FUSED=0, read
+ * once per process, takes the unfused forms of the two entries below; same words.
+ * FHE_EINVAL for everything fhe_direct_group_sum refuses so, a mode outside 0..3,
+ * left_lo given outside FHE_RUN_BETWEEN or missing in it, and a left_lo that is a
+ * stack or differs from left_key in level or slot count; FHE_EDEPTH, before any
+ * work, for a column above col_max_level and for a context without out_level
+ * levels.  On failure no output handle is set (every one is NULL). */
+#define FHE_RUN_ROWS 0
+#define FHE_RUN_LE 1
+#define FHE_RUN_LT 2
+#define FHE_RUN_BETWEEN 3
+int fhe_direct_running_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *left_lo /* NULL unless BETWEEN */,
+                           const fhe_ct *right_key, const fhe_ct *const *cols, int ncols, int mode, double eps, int N,
+                           const int32_t *rots, int nrot, int n, int dg, int df, fhe_ct **outs /* ncols handles */,
+                           fhe_ct **count_out /* may be NULL */);
+/* for tests and bindings: the bounded differences, member v count + i of the
+ * nbounds count stack = fhe_add_const(fhe_sub(as[v], bs[i]), consts[v]) word for
+ * word, nbounds = 1 or 2, written by one kernel that loads each bs[i] once for all
+ * bounds and the as once per four members (FHE_RUN_FUSED=0: the stacked
+ * differences per bound, then the constant in place).  The as share a level and
+ * so do the bs; as at a lower level are level-adjusted once, at a higher one every
+ * member takes its own operations. */
+int fhe_sub_bounds_stacked(fhe_ctx *ctx, const fhe_ct *const *as, int nbounds, const fhe_ct *const *bs, int count,
+                           const double *consts /* nbounds */, fhe_ct **out);
+/* and the products they feed: a (and a_sub) are stacks of B members, b_stack a
+ * column-major stack of ncols B members, all at one level; member p B + z of the
+ * result = fhe_mul_relin(fhe_add_const(member z of a, c), member p B + z of b_stack),
+ * resp. fhe_mul_relin(fhe_sub(member z of a, member z of a_sub), ...), word for word
+ * (one tensor pass that forms the left operand once per four columns and never
+ * writes it; FHE_RUN_FUSED=0: the left operand written out, then ncols products).
+ * FHE_EINVAL for member counts or levels that do not fit and ncols < 1. */
+int fhe_mul_pairs_const(fhe_ctx *ctx, const fhe_ct *a, double c, const fhe_ct *b_stack, int ncols,
+                        fhe_ct **out_stack);
+int fhe_mul_pairs_sub(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_sub, const fhe_ct *b_stack, int ncols,
+                      fhe_ct **out_stack);
+
 /* Lexicographic rank: order rows by several encrypted key columns (the project's
  * own extension, like fhe_direct_select and fhe_direct_group_sum).
  * keys[0] .. keys[nkeys - 1], most significant first, 2 <= nkeys <= 4, each a single
