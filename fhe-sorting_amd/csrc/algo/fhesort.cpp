@@ -2178,6 +2178,230 @@ std::vector<CtPtr> DirectSortN::runningSums(const Ciphertext &kl, const Cipherte
     return outs;
 }
 
+WindowSumLevels windowSumLevels(int key_level, int nfactors, int n, int dg, int df, int ps_split) {
+    if (nfactors < 2 || nfactors > 4)
+        throw std::invalid_argument("window sum: 2 to 4 factors, got " + std::to_string(nfactors));
+    const GroupSumLevels g = groupSumLevels(key_level, n, dg, df, ps_split);  // the same differences and sign
+    WindowSumLevels lv;
+    lv.sign_depth = g.sign_depth;
+    lv.diff_level = g.diff_level;
+    lv.match_level = g.match_level;
+    lv.prod_level = lv.match_level + (nfactors == 2 ? 1 : 2);  // the product tree's depth, ceil(log2 F)
+    lv.col_max_level = lv.prod_level - 2;
+    lv.out_level = lv.prod_level + 1;
+    return lv;
+}
+
+// Window sums.  runningSums' layout, key by key: slot s of batch b holds
+// K[s mod N] - K'[(s mod N + t) mod N], t = b P_ + s / N, for every partition key and
+// the order key, so the product of their indicators runs slot-wise on the sign
+// outputs of one pair.  Every indicator is a clean 2 or 0; the 2^-F rides on the
+// columns' level adjustment and the count pays it as its own mul_const per batch.
+std::vector<CtPtr> DirectSortN::windowSums(const std::vector<const Ciphertext *> &pl,
+                                           const std::vector<const Ciphertext *> &pr, const Ciphertext *ol,
+                                           const Ciphertext *olo, const Ciphertext *orr,
+                                           const std::vector<const Ciphertext *> &cols, int mode, double eps,
+                                           bool want_count, SignFunc f, const SignConfig &cfg) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)cols.size(), G = (int)pl.size();
+    if (mode < WinRows || mode > WinGroup)
+        throw std::invalid_argument("window sum: mode must lie in 0..4, got " + std::to_string(mode));
+    if (G < 1 || G > 3) throw std::invalid_argument("window sum: 1 to 3 partition keys, got " + std::to_string(G));
+    if ((int)pr.size() != G) throw std::invalid_argument("window sum: one right partition key per left one");
+    const int F = G + (mode != WinGroup ? 1 : 0);
+    if (F < 2) throw std::invalid_argument("window sum: one partition key without an order key is the group sum");
+    if (F > 4) throw std::invalid_argument("window sum: at most 4 factors, got " + std::to_string(F));
+    if (mode == WinGroup && (ol || orr || olo))
+        throw std::invalid_argument("window sum: an order key is given in the group mode");
+    if (mode != WinGroup && (!ol || !orr)) throw std::invalid_argument("window sum: the mode needs the order key");
+    if (mode == WinBetween && !olo) throw std::invalid_argument("window sum: the between mode needs the lower bound");
+    if (mode != WinBetween && olo)
+        throw std::invalid_argument("window sum: a lower bound is given outside the between mode");
+    if (P == 0 && !want_count) throw std::invalid_argument("window sum: neither a column nor the count is asked for");
+    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("window sum: eps must lie in (0, 0.5)");
+    std::vector<std::pair<std::string, const Ciphertext *>> keys;
+    for (int g = 0; g < G; ++g) {
+        keys.emplace_back("left partition key " + std::to_string(g), pl[g]);
+        keys.emplace_back("right partition key " + std::to_string(g), pr[g]);
+    }
+    if (ol) keys.emplace_back("left order key", ol);
+    if (orr) keys.emplace_back("right order key", orr);
+    if (olo) keys.emplace_back("lower bound", olo);
+    for (auto &k : keys) {
+        if (!k.second) throw std::invalid_argument("window sum: the " + k.first + " is null");
+        if (k.second->batch != 1) throw std::invalid_argument("window sum: the " + k.first + " is a stack");
+        if (k.second->slots != N)
+            throw std::invalid_argument("window sum: the " + k.first + " has " + std::to_string(k.second->slots) +
+                                        " slots, need " + std::to_string(N));
+        if (k.second->level != pl[0]->level || k.second->limbs != pl[0]->limbs)
+            throw std::invalid_argument("window sum: the keys sit at different levels (the " + k.first + " at " +
+                                        std::to_string(k.second->level) + ", left partition key 0 at " +
+                                        std::to_string(pl[0]->level) + ")");
+    }
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("window sum: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument("window sum: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->slots != N)
+            throw std::invalid_argument("window sum: column " + std::to_string(p) + " has " +
+                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(N));
+    }
+    const WindowSumLevels lv =
+        windowSumLevels(pl[0]->level, F, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
+    if (lv.out_level > cc.params().L)
+        throw std::runtime_error("window sum: " + std::to_string(F) + " factors on keys at level " +
+                                 std::to_string(pl[0]->level) + " need " + std::to_string(lv.out_level) +
+                                 " levels, the context has " + std::to_string(cc.params().L) + ": no levels left");
+    for (int p = 0; p < P; ++p)
+        if (cols[p]->level > lv.col_max_level)
+            throw std::runtime_error("window sum: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
+                                     std::to_string(lv.col_max_level) + "): no levels left to meet the indicator");
+    if (!cache_masks) refresh_masks();
+    std::optional<AlgoPhase> ph;
+    ph.emplace("win_baby");
+    const int K = G + (orr ? 1 : 0);  // right keys to shift: the partition keys, then the order key
+    std::vector<std::vector<CtPtr>> kbaby(K);
+    for (int k = 0; k < K; ++k) {
+        kbaby[k] = babySteps(k < G ? *pr[k] : *orr, s.np);
+        for (auto &b : kbaby[k]) b->slots = s.num_slots;
+    }
+    // the columns, prepared as groupSums prepares them: 2^-F on the way to the level below the indicators' product
+    std::vector<std::vector<CtPtr>> cbaby(P);
+    for (int p = 0; p < P; ++p) {
+        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 1.0 / (double)(1 << F), lv.prod_level - 1), s.np);
+        for (auto &b : cbaby[p]) b->slots = s.num_slots;
+    }
+    ph.reset();
+    std::vector<int> mine(s.num_batch);
+    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
+    auto dup_of = [&](const Ciphertext &x) {
+        CtPtr d = cc.clone(x);
+        d->slots = s.num_slots;
+        return d;
+    };
+    std::vector<CtPtr> dups;
+    std::vector<const Ciphertext *> dp;
+    for (int g = 0; g < G; ++g) {
+        dups.push_back(dup_of(*pl[g]));
+        dp.push_back(dups.back().get());
+    }
+    CtPtr dup_o = ol ? dup_of(*ol) : nullptr, dup_lo = olo ? dup_of(*olo) : nullptr;
+    // WinRows: the offsets E_b of this call's eps, at the level the differences sit at
+    std::map<int, PtPtr> offs;
+    if (mode == WinRows) offs = tiebreakOffsets(s.num_slots, mine, lv.diff_level, eps);
+    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
+    const int V = mode == WinGroup ? 0 : mode == WinBetween ? 2 : 1;  // the order key's sign members per batch
+    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / (2 * G + V));
+    // columns per stacked product, as rotationIndexCheckColumns bounds them
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
+    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
+    const double scale_down = 1.0 / (double)(1 << F);
+    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level prod_level + 1)
+    std::mutex cnt_mu;
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph("win_batches");
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        CtPtr cnt;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr sg;
+            {
+                std::vector<CtPtr> shifted;  // key-major: the partition keys, then the order key
+                for (int k = 0; k < K; ++k)
+                    for (auto &x : vecRotsOptMany(L, kbaby[k], s.num_partition, s.num_slots, s.np, iss))
+                        shifted.push_back(x);
+                std::vector<const Ciphertext *> pb, ob;
+                for (int i = 0; i < G * B; ++i) pb.push_back(shifted[(size_t)i].get());
+                for (int i = G * B; i < K * B; ++i) ob.push_back(shifted[(size_t)i].get());
+                std::vector<const Plaintext *> es;
+                if (mode == WinRows)
+                    for (int b : iss) es.push_back(offs.at(b).get());
+                CtPtr d = E.sub_window_stacked(dp, pb, dup_o.get(), dup_lo.get(), ob, es, mode == WinLT ? -eps : eps, eps);
+                shifted.clear();
+                sg = sign(*d, E, f, cfg);
+            }
+            if (sg->level != lv.match_level) throw std::logic_error("window sum: unexpected sign output level");
+            auto view = [&](int first) {  // B members of the sign's stack from member `first` on
+                Ciphertext v = *sg;
+                v.batch = B;
+                v.data = sg->data + (size_t)first * 2 * sg->limbs * E.n();
+                return v;
+            };
+            // M_g R: (u_g - w_g) (s + 1), or (u_g - w_g) (u' - w') between two bounds
+            auto withOrder = [&](int g) {
+                const Ciphertext u = view(2 * g * B), w = view((2 * g + 1) * B), so = view(2 * G * B);
+                return mode == WinBetween ? E.mul_sub_sub(u, w, so, view((2 * G + 1) * B)) : E.mul_lex(so, 1.0, u, w);
+            };
+            auto twoKeys = [&](int g, int h) {  // M_g M_h
+                return E.mul_sub_sub(view(2 * g * B), view((2 * g + 1) * B), view(2 * h * B), view((2 * h + 1) * B));
+            };
+            CtPtr A;
+            if (F == 2) {
+                A = mode == WinGroup ? twoKeys(0, 1) : withOrder(0);
+            } else if (F == 3) {  // M_0 meets the inner product one level above it: sub, then the product adjusts it
+                CtPtr inner = mode == WinGroup ? twoKeys(1, 2) : withOrder(1);
+                A = E.mul(*E.sub(view(0), view(B)), *inner);
+            } else {
+                CtPtr left = twoKeys(0, 1), right = withOrder(2);
+                A = E.mul(*left, *right);
+            }
+            if (A->level != lv.prod_level) throw std::logic_error("window sum: unexpected indicator level");
+            if (want_count) {
+                CtPtr c = E.mul_const(*A, scale_down);
+                E.add_inplace(cnt, B == 1 ? *c : *E.sum_members(*c));
+            }
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
+                for (int p = p0; p < p0 + Pg; ++p)
+                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
+                // the stacked column product with nothing added to the indicator: mul(A_z, column)'s words
+                CtPtr prod = E.mul_pairs_const(*A, 0.0, *asStack(E, sv), Pg);
+                sv.clear();
+                E.sum_member_groups(*prod, Pg, accs[g]);
+            }
+        }
+        if (cnt) {
+            std::lock_guard<std::mutex> lk(cnt_mu);
+            cnt_parts.push_back(cnt);
+        }
+        if (bs.empty() || P == 0) return nullptr;
+        if (accs.size() == 1) return accs[0];
+        std::vector<const Ciphertext *> all;
+        for (auto &a : accs) all.push_back(a.get());
+        return E.stack(all);  // the column groups, in column order
+    });
+    CtPtr out, cnt;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(out, *p);
+    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    cnt_parts.clear();
+    AlgoPhase fold_ph("win_fold");
+    auto fold = [&](CtPtr &v) {
+        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    };
+    std::vector<CtPtr> outs;
+    if (P > 0) {
+        fold(out);
+        for (int p = 0; p < P; ++p) {
+            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
+            outs.back()->slots = N;
+        }
+    }
+    if (want_count) {
+        fold(cnt);
+        outs.push_back(cnt);
+        outs.back()->slots = N;
+    }
+    return outs;
+}
+
 LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split) {
     if (nkeys < 2 || nkeys > 4) throw std::invalid_argument("lex rank: 2 to 4 keys, got " + std::to_string(nkeys));
     const GroupSumLevels g = groupSumLevels(key_level, n, dg, df, ps_split);  // the same differences and sign

@@ -210,6 +210,20 @@ struct LexRankLevels {
 };
 LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
 
+// Levels of DirectSortN::windowSums for keys at key_level and nfactors pair
+// indicators (2..4: the partition keys, plus one for an order key) under the
+// composite sign (n, dg, df): the differences at diff_level = key_level + 1, every
+// sign output at match_level = diff_level + sign_depth, the indicators' product
+// after a tree of ceil(log2 nfactors) products at prod_level, the columns brought
+// to prod_level - 1 before their own masked sum, so a column may sit at
+// col_max_level = prod_level - 2 at most, and every output at out_level =
+// prod_level + 1.  Throws std::invalid_argument on a factor count outside 2..4, a
+// negative level or a sign the GPU path lacks.
+struct WindowSumLevels {
+    int sign_depth, diff_level, match_level, prod_level, col_max_level, out_level;
+};
+WindowSumLevels windowSumLevels(int key_level, int nfactors, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
+
 // Sums a ciphertext's u64 limbs over ranks in place (device pointer, count
 // u64); the engine reduces mod q afterwards.  nullptr = single rank.
 using CtAllReduce = std::function<void(u64 *dev_data, size_t count)>;
@@ -350,6 +364,31 @@ class DirectSortN {
     std::vector<CtPtr> runningSums(const Ciphertext &kl, const Ciphertext *lo, const Ciphertext &kr,
                                    const std::vector<const Ciphertext *> &cols, int mode, double eps, bool want_count,
                                    SignFunc f, const SignConfig &cfg);
+    // Window sums (the project's own extension): the running sums
+    // restricted to the rows that agree on every partition key.  With G = pl.size()
+    // partition keys (1..3; pl[g] the left table's, pr[g] the right table's), an
+    // optional order key (ol, orr, and olo for WinBetween) and P = cols.size(),
+    // out[p] holds at slot e  sum_j c_ej cols[p]_j  and want_count appends sum_j c_ej,
+    //   c_ej = prod_g [pl[g]_e = pr[g]_j] * [the mode selects j for e],
+    // the partition indicator being (sign(d + eps) - sign(d - eps)) / 2 and the order
+    // key's runningSums' for the mode (WinRows .. WinBetween = RunRows .. RunBetween);
+    // WinGroup has no order key (GROUP BY a, b; the join on several keys) and needs
+    // G >= 2.  F = G + (mode != WinGroup) factors, 2 <= F <= 4.  Levels:
+    // windowSumLevels.  runningSums' layout, chunking (a chunk's sign runs over
+    // 2 G + V members per batch, V = 0, 1 or 2), lanes and column groups; the
+    // columns ride 2^-F on their way to prod_level - 1.  One
+    // Engine::sub_window_stacked and one sign per chunk, the factor products on views
+    // of the sign's stack (Engine::mul_sub_sub, mul_lex; an outer product of operands
+    // at two levels takes sub and mul), then the column product.  Needs runningSums'
+    // conditions on every key.  A column above col_max_level or a context without
+    // out_level levels is refused before any work.  The words do not depend on
+    // max_stack, lanes, max_col_members or cache_masks.  Unsharded; `tiebreak` has no
+    // effect.
+    enum WinMode { WinRows = 0, WinLE = 1, WinLT = 2, WinBetween = 3, WinGroup = 4 };
+    std::vector<CtPtr> windowSums(const std::vector<const Ciphertext *> &pl, const std::vector<const Ciphertext *> &pr,
+                                  const Ciphertext *ol, const Ciphertext *olo, const Ciphertext *orr,
+                                  const std::vector<const Ciphertext *> &cols, int mode, double eps, bool want_count,
+                                  SignFunc f, const SignConfig &cfg);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;

@@ -924,6 +924,131 @@ int fhe_mul_pairs_sub(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_sub, const 
         *out_stack = wrap(ctx->eng->mul_pairs_sub(*a->p, *a_sub->p, *b_stack->p, ncols));
     });
 }
+int fhe_direct_window_sum(fhe_ctx *ctx, const fhe_ct *const *part_left, const fhe_ct *const *part_right, int nparts,
+                          const fhe_ct *order_left, const fhe_ct *order_lo, const fhe_ct *order_right,
+                          const fhe_ct *const *cols, int ncols, int mode, double eps, int N, const int32_t *rots,
+                          int nrot, int n, int dg, int df, fhe_ct **outs, fhe_ct **count_out) {
+    if (outs)
+        for (int p = 0; p < ncols; ++p) outs[p] = nullptr;
+    if (count_out) *count_out = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        const std::string me = "fhe_direct_window_sum: ";
+        if (mode < FHE_WIN_ROWS || mode > FHE_WIN_GROUP)
+            throw std::invalid_argument(me + "mode must lie in 0..4, got " + std::to_string(mode));
+        if (nparts < 1 || nparts > 3)
+            throw std::invalid_argument(me + "nparts must lie in 1..3, got " + std::to_string(nparts));
+        const int F = nparts + (mode != FHE_WIN_GROUP ? 1 : 0);
+        if (F < 2) throw std::invalid_argument(me + "one partition key under FHE_WIN_GROUP is fhe_direct_group_sum");
+        if (F > 4) throw std::invalid_argument(me + "at most 4 factors, got " + std::to_string(F));
+        if (!part_left || !part_right) throw std::invalid_argument(me + "null partition key array");
+        if (mode == FHE_WIN_GROUP && (order_left || order_right || order_lo))
+            throw std::invalid_argument(me + "an order key is given under FHE_WIN_GROUP");
+        if (mode != FHE_WIN_GROUP && (!order_left || !order_left->p || !order_right || !order_right->p))
+            throw std::invalid_argument(me + "the mode needs order_left and order_right");
+        if (mode == FHE_WIN_BETWEEN && (!order_lo || !order_lo->p))
+            throw std::invalid_argument(me + "FHE_WIN_BETWEEN needs order_lo, the lower bound");
+        if (mode != FHE_WIN_BETWEEN && order_lo)
+            throw std::invalid_argument(me + "order_lo is given outside FHE_WIN_BETWEEN");
+        if (ncols < 0) throw std::invalid_argument(me + "ncols must be >= 0");
+        if (ncols == 0 && !count_out) throw std::invalid_argument(me + "neither a column nor the count is asked for");
+        if (ncols > 0 && (!cols || !outs)) throw std::invalid_argument(me + "null column or output array");
+        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument(me + "eps must lie in (0, 0.5)");
+        std::vector<const Ciphertext *> pl, pr, v;
+        for (int g = 0; g < nparts; ++g) {
+            if (!part_left[g] || !part_left[g]->p)
+                throw std::invalid_argument(me + "left partition key " + std::to_string(g) + " is null");
+            if (!part_right[g] || !part_right[g]->p)
+                throw std::invalid_argument(me + "right partition key " + std::to_string(g) + " is null");
+            pl.push_back(part_left[g]->p.get());
+            pr.push_back(part_right[g]->p.get());
+        }
+        for (int p = 0; p < ncols; ++p) {
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(me + "column " + std::to_string(p) + " is null");
+            v.push_back(cols[p]->p.get());
+        }
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = 0;  // unsharded, like the running sums
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        // the shape refusals (stacks, slot counts, levels) and the depth refusals (a column
+        // too deep, a context too shallow) are raised by the operator before it starts any work
+        std::vector<CtPtr> r = ds.windowSums(pl, pr, order_left ? order_left->p.get() : nullptr,
+                                             order_lo ? order_lo->p.get() : nullptr,
+                                             order_right ? order_right->p.get() : nullptr, v, mode, eps,
+                                             count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
+        if (count_out) *count_out = wrap(r[(size_t)ncols]);
+    });
+}
+int fhe_window_sum_levels(int key_level, int nfactors, int n, int dg, int df, int *col_max_level, int *out_level) {
+    return guard([&] {
+        const WindowSumLevels lv = windowSumLevels(key_level, nfactors, n, dg, df);
+        if (col_max_level) *col_max_level = lv.col_max_level;
+        if (out_level) *out_level = lv.out_level;
+    });
+}
+int fhe_sub_window_stacked(fhe_ctx *ctx, const fhe_ct *const *part_as, int nparts, const fhe_ct *const *part_bs,
+                           int count, int mode, const fhe_ct *order_a, const fhe_ct *order_lo,
+                           const fhe_ct *const *order_bs, const fhe_pt *const *ps, double eps, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(part_as);
+        NEED(part_bs);
+        NEED(out);
+        if (nparts < 1 || nparts > 3) throw std::invalid_argument("fhe_sub_window_stacked: nparts must lie in 1..3");
+        if (count < 1) throw std::invalid_argument("fhe_sub_window_stacked: count must be >= 1");
+        if (mode < FHE_WIN_ROWS || mode > FHE_WIN_GROUP)
+            throw std::invalid_argument("fhe_sub_window_stacked: mode must lie in 0..4");
+        if ((mode != FHE_WIN_GROUP) != (order_a != nullptr && order_bs != nullptr))
+            throw std::invalid_argument("fhe_sub_window_stacked: order_a and order_bs go with every mode but FHE_WIN_GROUP");
+        if ((mode == FHE_WIN_BETWEEN) != (order_lo != nullptr))
+            throw std::invalid_argument("fhe_sub_window_stacked: order_lo goes with FHE_WIN_BETWEEN alone");
+        if ((mode == FHE_WIN_ROWS) != (ps != nullptr))
+            throw std::invalid_argument("fhe_sub_window_stacked: the offsets ps go with FHE_WIN_ROWS alone");
+        std::vector<const Ciphertext *> a, b, ob;
+        std::vector<const Plaintext *> p;
+        for (int g = 0; g < nparts; ++g) {
+            NEED(part_as[g]);
+            a.push_back(part_as[g]->p.get());
+        }
+        for (int i = 0; i < nparts * count; ++i) {
+            NEED(part_bs[i]);
+            b.push_back(part_bs[i]->p.get());
+        }
+        if (order_bs && mode != FHE_WIN_GROUP)
+            for (int i = 0; i < count; ++i) {
+                NEED(order_bs[i]);
+                ob.push_back(order_bs[i]->p.get());
+            }
+        if (ps)
+            for (int i = 0; i < count; ++i) {
+                NEED(ps[i]);
+                p.push_back(ps[i]->p.get());
+            }
+        *out = wrap(ctx->eng->sub_window_stacked(a, b, order_a ? order_a->p.get() : nullptr,
+                                                 order_lo ? order_lo->p.get() : nullptr, ob, p,
+                                                 mode == FHE_WIN_LT ? -eps : eps, eps));
+    });
+}
+int fhe_mul_sub_sub(fhe_ctx *ctx, const fhe_ct *u, const fhe_ct *w, const fhe_ct *u2, const fhe_ct *w2, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(u);
+        NEED(w);
+        NEED(u2);
+        NEED(w2);
+        NEED(out);
+        *out = wrap(ctx->eng->mul_sub_sub(*u->p, *w->p, *u2->p, *w2->p));
+    });
+}
 int fhe_direct_lex_rank(fhe_ctx *ctx, const fhe_ct *const *keys, int nkeys, double eps, int N, const int32_t *rots,
                         int nrot, int n, int dg, int df, fhe_ct **rank) {
     if (rank) *rank = nullptr;

@@ -1748,6 +1748,127 @@ __global__ __launch_bounds__(NT) void k_tensor_run(u64 *d01, u64 *d2, const u64 
     }
 }
 
+// The sign arguments of a chunk of comparator batches under G partition keys and
+// an optional order key (windowSums), all written straight into
+// one stack of (2 G + V) `count` members.  Slot g < G is a partition key: with
+// d = a_g - b_{g, i}, member (2 g) count + i = d with Kp 2^shp (+eps) added to c0 and
+// member (2 g + 1) count + i = d with Kn 2^shn (-eps), both from one load of b.  Slot
+// G is the order key, by `kind`: 1 writes member 2 G count + i = d with Ko 2^sho added
+// to c0 (LE / LT), 2 the same with p_i added to c0 (ROWS), 3 the two bounds
+// a_G - b + eps and a2 - b - eps as members 2 G count + i and (2 G + 1) count + i from
+// one load of b (BETWEEN).  A left operand's words are loaded once per tile of
+// SWN_TM members: a two-sided slot moves 6 B + 2 ceil(B / TM) limb-units (BETWEEN
+// 6 B + 4 ceil(B / TM)) against the 14 B of sub_stacked and two add_consts, a
+// one-sided slot 4 B + 2 ceil(B / TM) (5 B with offsets) against 8 B (9 B).
+// sub_mod, then add_mod of the constant's residue or of the plaintext: the
+// words of k_sub and k_c0_op (modes 0 and 1).  A last tile narrower than SWN_TM
+// repeats its last member and stores only the valid ones.
+// grid: x = coefficient block, y = limb, z = slot * tiles + tile.
+constexpr int SWN_TM = 4;
+constexpr int SWN_SLOTS = 4;
+struct SubWinArgs {
+    const u64 *a[SWN_SLOTS];
+    const u64 *a2;              // kind 3: the lower bound
+    const u64 *b[LIN_MAX];      // slot-major: b[slot * B + i]
+    const u64 *p[LIN_MAX / 2];  // kind 2: the order key's offsets (B of them)
+    int G, B, kind;
+};
+__global__ __launch_bounds__(NT) void k_sub_window_stacked(u64 *out, SubWinArgs A, size_t count, int64_t Kp, int shp,
+                                                           int64_t Kn, int shn, int64_t Ko, int sho, size_t ln_all,
+                                                           const Mod *mods, int logN) {
+    constexpr int TM = SWN_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int tiles = (A.B + TM - 1) / TM;
+    const int slot = (int)(blockIdx.z / (unsigned)tiles), m0 = (int)(blockIdx.z % (unsigned)tiles) * TM;  // block-uniform
+    const bool bounds = slot == A.G && A.kind == 3;
+    const u64 *ap = A.a[slot];
+    const ulonglong2 a0 = ld2(ap + lo), a1 = ld2(ap + ln_all + lo);
+    ulonglong2 c0 = a0, c1 = a1;  // the -eps side's left operand: a itself unless the slot holds two bounds
+    if (bounds) {
+        c0 = ld2(A.a2 + lo);
+        c1 = ld2(A.a2 + ln_all + lo);
+    }
+    ulonglong2 b0[TM], b1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const u64 *bp = A.b[slot * A.B + min(m0 + t, A.B - 1)];
+        b0[t] = ld2(bp + lo);
+        b1[t] = ld2(bp + ln_all + lo);
+    }
+    if (slot < A.G || bounds) {  // two sides: +eps on a - b, -eps on c - b
+        const u64 wp = smod(Kp, shp, mods[l]), wn = smod(Kn, shn, mods[l]);
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < A.B) {
+                u64 *o = out + ((size_t)(2 * slot) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, make_ulonglong2(add_mod(sub_mod(a0.x, b0[t].x, q), wp, q),
+                                       add_mod(sub_mod(a0.y, b0[t].y, q), wp, q)));
+                st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
+                u64 *om = o + count * 2 * ln_all;
+                st2(om, make_ulonglong2(add_mod(sub_mod(c0.x, b0[t].x, q), wn, q),
+                                        add_mod(sub_mod(c0.y, b0[t].y, q), wn, q)));
+                st2(om + ln_all, make_ulonglong2(sub_mod(c1.x, b1[t].x, q), sub_mod(c1.y, b1[t].y, q)));
+            }
+    } else {  // one side: the constant, or the member's plaintext offset
+        const bool plain = A.kind == 2;
+        ulonglong2 p[TM];
+        if (plain) {
+#pragma unroll
+            for (int t = 0; t < TM; ++t) p[t] = ld2(A.p[min(m0 + t, A.B - 1)] + lo);
+        }
+        const u64 wo = smod(Ko, sho, mods[l]);
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < A.B) {
+                ulonglong2 d0 = make_ulonglong2(sub_mod(a0.x, b0[t].x, q), sub_mod(a0.y, b0[t].y, q));
+                d0 = plain ? make_ulonglong2(add_mod(d0.x, p[t].x, q), add_mod(d0.y, p[t].y, q))
+                           : make_ulonglong2(add_mod(d0.x, wo, q), add_mod(d0.y, wo, q));
+                u64 *o = out + ((size_t)(2 * slot) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, d0);
+                st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
+            }
+    }
+}
+
+// k_tensor with both operands formed on load (windowSums' factor products,
+// DESIGN.md §6.7): member z's left operand is u_z - w_z, its right operand
+// u2_z - w2_z (k_sub's sub_mod on both polynomials), so neither difference is
+// written to memory: 11 limb-units per member against the 6 + 6 + 7 of two subs
+// and k_tensor.  u, w, u2 and w2 are stacks of one level, members at stride sa.
+__global__ __launch_bounds__(NT) void k_tensor_win(u64 *d01, u64 *d2, const u64 *u, const u64 *w, const u64 *u2,
+                                                   const u64 *w2, size_t ln_all, size_t sa, const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod m = mods[l];
+    const size_t z = blockIdx.z, o = (size_t)l * n + k;
+    const u64 *U = u + z * sa, *W = w + z * sa, *U2 = u2 + z * sa, *W2 = w2 + z * sa;
+    const ulonglong2 u0 = ld2(U + o), u1 = ld2(U + ln_all + o);
+    const ulonglong2 w0 = ld2(W + o), w1 = ld2(W + ln_all + o);
+    const ulonglong2 x0 = ld2(U2 + o), x1 = ld2(U2 + ln_all + o);
+    const ulonglong2 y0 = ld2(W2 + o), y1 = ld2(W2 + ln_all + o);
+    const ulonglong2 a0 = make_ulonglong2(sub_mod(u0.x, w0.x, m.q), sub_mod(u0.y, w0.y, m.q));
+    const ulonglong2 a1 = make_ulonglong2(sub_mod(u1.x, w1.x, m.q), sub_mod(u1.y, w1.y, m.q));
+    const ulonglong2 b0 = make_ulonglong2(sub_mod(x0.x, y0.x, m.q), sub_mod(x0.y, y0.y, m.q));
+    const ulonglong2 b1 = make_ulonglong2(sub_mod(x1.x, y1.x, m.q), sub_mod(x1.y, y1.y, m.q));
+    ulonglong2 e0, e1, e2;
+    e0.x = mul_barrett(a0.x, b0.x, m);
+    e0.y = mul_barrett(a0.y, b0.y, m);
+    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
+    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
+    e2.x = mul_barrett(a1.x, b1.x, m);
+    e2.y = mul_barrett(a1.y, b1.y, m);
+    st2(d01 + z * 2 * ln_all + o, e0);
+    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
+    st2(d2 + z * ln_all + o, e2);
+}
+
 // grid: x = n / NT, y = limb, z = segment
 __global__ __launch_bounds__(NT) void k_permute(u64 *out, const u64 *in, const uint32_t *perm, Seg S, int logN) {
     const size_t n = (size_t)1 << logN;
@@ -3695,6 +3816,51 @@ void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, 
             launch_clocked(inst_name<TC_PC, 0>("k_tensor_run"), B, k_tensor_run<TC_PC, 0>,
                            ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all,
                            a, w, b + mo * 2 * ln_all, ln_all, sa, K, sh, Pn, members, mods, logN);
+    }
+}
+int sub_window_tile() { return SWN_TM; }
+void ew_sub_window_stacked(u64 *out, const u64 *const *as, int parts, const u64 *a2, const u64 *const *bs,
+                           const u64 *const *ps, int kind, int count, int64_t Kp, int shp, int64_t Kn, int shn,
+                           int64_t Ko, int sho, int limbs, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || count <= 0) return;
+    const int slots = parts + (kind ? 1 : 0);
+    if (parts < 1 || slots > SWN_SLOTS) throw std::invalid_argument("ew_sub_window_stacked: unsupported key count");
+    if (kind < 0 || kind > 3 || (kind == 2) != (ps != nullptr) || (kind == 3) != (a2 != nullptr))
+        throw std::invalid_argument("ew_sub_window_stacked: the order key's operands do not fit its kind");
+    const size_t ln_all = (size_t)limbs << logN;
+    // operands of one launch: slots * B pointers in b, B in p
+    const int per_launch = std::min(LIN_MAX / slots, LIN_MAX / 2);
+    for (int base = 0; base < count; base += per_launch) {
+        SubWinArgs A{};
+        A.G = parts;
+        A.B = std::min(per_launch, count - base);
+        A.kind = kind;
+        A.a2 = a2;
+        for (int s = 0; s < slots; ++s) {
+            A.a[s] = as[s];
+            for (int i = 0; i < A.B; ++i) A.b[s * A.B + i] = bs[(size_t)s * count + base + i];
+        }
+        if (ps)
+            for (int i = 0; i < A.B; ++i) A.p[i] = ps[base + i];
+        const int tiles = (A.B + SWN_TM - 1) / SWN_TM;
+        const double order = kind == 0   ? 0.0
+                             : kind == 3 ? 6.0 * A.B + 4.0 * tiles
+                                         : (kind == 2 ? 5.0 : 4.0) * A.B + 2.0 * tiles;
+        const double B = 8.0 * (parts * (6.0 * A.B + 2.0 * tiles) + order) * ln_all;
+        launch_clocked("k_sub_window_stacked", B, k_sub_window_stacked, ew_grid(logN, limbs, slots * tiles), dim3(NT), st,
+                       out + (size_t)base * 2 * ln_all, A, (size_t)count, Kp, shp, Kn, shn, Ko, sho, ln_all, mods, logN);
+    }
+}
+void ew_tensor_win(u64 *d01, u64 *d2, const u64 *u, const u64 *w, const u64 *u2, const u64 *w2, int limbs, int members,
+                   size_t sa, const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int base = 0; base < members; base += 65535) {  // grid z limit
+        const int cnt = std::min(65535, members - base);
+        const double B = 8.0 * 11.0 * cnt * ln_all;
+        launch_clocked("k_tensor_win", B, k_tensor_win, ew_grid(logN, limbs, cnt), dim3(NT), st,
+                       d01 + (size_t)base * 2 * ln_all, d2 + (size_t)base * ln_all, u + (size_t)base * sa,
+                       w + (size_t)base * sa, u2 + (size_t)base * sa, w2 + (size_t)base * sa, ln_all, sa, mods, logN);
     }
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,

@@ -319,6 +319,24 @@ void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64
 // operand is formed once per tensor_pairs_per_thread() columns.
 void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, int P, int limbs, int members,
                    size_t sa, int64_t K, int sh, const Mod *mods, int logN, hipStream_t st);
+// The sign arguments of `parts` partition keys and an optional order key against
+// `count` shifted operands each (bs slot-major, all [2][limbs][n]) in one pass.
+// Slot g < parts: members (2 g) count + i and (2 g + 1) count + i of out = as[g] - bs[g][i]
+// with Kp 2^shp resp. Kn 2^shn added to c0.  The order key is slot `parts`, by kind:
+// 0 none; 1 member 2 parts count + i = as[parts] - bs[parts][i] with Ko 2^sho added to c0;
+// 2 the same with ps[i] added to c0 instead; 3 members 2 parts count + i = as[parts] - b
+// with Kp 2^shp and (2 parts + 1) count + i = a2 - b with Kn 2^shn.  A thread loads each
+// operand once and applies a left operand's words to up to sub_window_tile() members;
+// word for word ew_sub, then ew_c0_op mode 0 or 1, per member.
+int sub_window_tile();
+void ew_sub_window_stacked(u64 *out, const u64 *const *as, int parts, const u64 *a2, const u64 *const *bs,
+                           const u64 *const *ps, int kind, int count, int64_t Kp, int shp, int64_t Kn, int shn,
+                           int64_t Ko, int sho, int limbs, const Mod *mods, int logN, hipStream_t st);
+// ew_tensor with both operands formed on load: member z of d01 / d2 holds the tensor
+// of (u[z] - w[z], u2[z] - w2[z]); the four are stacks of `members` members at stride
+// sa.  Word for word ew_sub twice, then ew_tensor.
+void ew_tensor_win(u64 *d01, u64 *d2, const u64 *u, const u64 *w, const u64 *u2, const u64 *w2, int limbs, int members,
+                   size_t sa, const Mod *mods, int logN, hipStream_t st);
 // out[l][k] = in[l][perm[k]]
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st);

@@ -2861,6 +2861,139 @@ CtPtr Engine::mul_pairs_left(const char *what, const Ciphertext &a, const Cipher
     I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
     return r;
 }
+// FHE_WIN_FUSED (A/B, default 1): the one-pass kernels of sub_window_stacked and mul_sub_sub
+static bool win_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_WIN_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+CtPtr Engine::sub_window_stacked(const std::vector<const Ciphertext *> &part_as,
+                                 const std::vector<const Ciphertext *> &part_bs, const Ciphertext *order_a,
+                                 const Ciphertext *order_lo, const std::vector<const Ciphertext *> &order_bs,
+                                 const std::vector<const Plaintext *> &ps, double order_const, double eps) {
+    const int G = (int)part_as.size();
+    if (G < 1 || G > 3) throw std::invalid_argument("sub_window_stacked: 1 to 3 partition keys");
+    if (part_bs.empty() || part_bs.size() % (size_t)G)
+        throw std::invalid_argument("sub_window_stacked: one operand list per partition key");
+    const int B = (int)(part_bs.size() / (size_t)G);
+    if (!order_a && (order_lo || !order_bs.empty() || !ps.empty()))
+        throw std::invalid_argument("sub_window_stacked: order operands without an order key");
+    if (order_a && (int)order_bs.size() != B)
+        throw std::invalid_argument("sub_window_stacked: one order operand per partition operand");
+    if (!ps.empty() && ((int)ps.size() != B || order_lo))
+        throw std::invalid_argument("sub_window_stacked: one plaintext per operand, and none beside a lower bound");
+    const int kind = !order_a ? 0 : order_lo ? 3 : !ps.empty() ? 2 : 1;
+    std::vector<const Ciphertext *> as = part_as, bs = part_bs;
+    if (order_a) {
+        as.push_back(order_a);
+        bs.insert(bs.end(), order_bs.begin(), order_bs.end());
+    }
+    if (order_lo) as.push_back(order_lo);
+    for (auto *a : as)
+        if (!a || a->batch != 1 || a->level != as[0]->level || a->limbs != as[0]->limbs || a->slots != as[0]->slots)
+            throw std::invalid_argument("sub_window_stacked: the keys must be single ciphertexts at one level");
+    for (auto *b : bs)
+        if (!b || b->batch != 1 || b->level != bs[0]->level)
+            throw std::invalid_argument("sub_window_stacked: operands differ in level");
+    // the plaintexts meet the differences, which sit at the deeper of the two levels
+    const int level = std::max(as[0]->level, bs[0]->level);
+    for (auto *p : ps)
+        if (!p || p->level != level) throw std::invalid_argument("sub_window_stacked: level mismatch");
+    const bool above = as[0]->level > bs[0]->level;  // every b would be adjusted: per-member ops, as sub_stacked
+    if (above || !win_fused_enabled()) {
+        std::vector<CtPtr> keep;
+        // member i of one side: add_const(sub(a, b_i), c); the plain form takes the stacked differences
+        auto side = [&](const Ciphertext &a, const std::vector<const Ciphertext *> &bl, double c) {
+            if (above) {
+                for (auto *b : bl) keep.push_back(add_const(*sub(a, *b), c));
+            } else {
+                CtPtr d = sub_stacked(a, bl);
+                add_const_inplace(d, c);
+                keep.push_back(d);
+            }
+        };
+        for (int g = 0; g < G; ++g) {
+            const std::vector<const Ciphertext *> bl(part_bs.begin() + (size_t)g * B, part_bs.begin() + (size_t)(g + 1) * B);
+            side(*part_as[g], bl, eps);
+            side(*part_as[g], bl, -eps);
+        }
+        if (kind == 1) {
+            side(*order_a, order_bs, order_const);
+        } else if (kind == 2) {
+            CtPtr d = above ? nullptr : sub_stacked(*order_a, order_bs);
+            for (int i = 0; i < B; ++i)
+                keep.push_back(add_plain(above ? *sub(*order_a, *order_bs[i]) : *member(*d, i), *ps[i]));
+        } else if (kind == 3) {
+            side(*order_a, order_bs, eps);
+            side(*order_lo, order_bs, -eps);
+        }
+        std::vector<const Ciphertext *> v;
+        for (auto &x : keep) v.push_back(x.get());
+        return stack(v);
+    }
+    std::vector<CtPtr> adj;  // sub(a, b) adjusts a the same way
+    std::vector<const u64 *> ap, bp, pp;
+    for (auto *a : as) {
+        if (a->level < level) {
+            adj.push_back(level_adjust(*a, level));
+            a = adj.back().get();
+        }
+        ap.push_back(a->data);
+    }
+    const Ciphertext &a0 = adj.empty() ? *as[0] : *adj[0];
+    const size_t ell = a0.limbs;
+    for (auto *b : bs) {
+        if (b->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_window_stacked: operand limb count differs from its level's");
+        bp.push_back(b->data);
+    }
+    for (auto *p : ps) {
+        if (p->limbs != ell)
+            throw std::invalid_argument("sub_window_stacked: plaintext limb count differs from its level's");
+        pp.push_back(p->data);
+    }
+    const int V = kind == 0 ? 0 : kind == 3 ? 2 : 1;
+    auto r = new_ct(a0.level, a0.slots, a0.scale, ell, (2 * G + V) * B);
+    const host::SConst Kp = host::const_at_scale(eps, a0.scale), Kn = host::const_at_scale(-eps, a0.scale);
+    const host::SConst Ko = kind == 1 ? host::const_at_scale(order_const, a0.scale) : host::SConst{};
+    dev::ew_sub_window_stacked(r->data, ap.data(), G, kind == 3 ? ap[(size_t)G + 1] : nullptr, bp.data(),
+                               pp.empty() ? nullptr : pp.data(), kind, B, Kp.k, Kp.sh, Kn.k, Kn.sh, Ko.k, Ko.sh, (int)ell,
+                               MODS, LOGN, ST);
+    const int tile = dev::sub_window_tile();
+    const double tiles = (double)((B + tile - 1) / tile);
+    const double order = kind == 0   ? 0.0
+                         : kind == 3 ? 6.0 * ell * B + 4.0 * ell * tiles
+                                     : (kind == 2 ? 5.0 : 4.0) * ell * B + 2.0 * ell * tiles;
+    count_bytes(G * (6.0 * ell * B + 2.0 * ell * tiles) + order, 1);
+    return r;
+}
+CtPtr Engine::mul_sub_sub(const Ciphertext &u, const Ciphertext &w, const Ciphertext &u2, const Ciphertext &w2) {
+    auto &I = *impl;
+    if (u.batch < 1 || w.batch != u.batch || u2.batch != u.batch || w2.batch != u.batch)
+        throw std::invalid_argument("mul_sub_sub: the operands differ in member count");
+    if (w.level != u.level || w.limbs != u.limbs) throw std::invalid_argument("mul_sub_sub: u and w differ in level");
+    if (w2.level != u2.level || w2.limbs != u2.limbs) throw std::invalid_argument("mul_sub_sub: u2 and w2 differ in level");
+    // the plain form (A/B), and operands at two levels (mul level-adjusts one): every step an op of its own
+    if (!win_fused_enabled() || u2.level != u.level || u2.limbs != u.limbs) return mul(*sub(u, w), *sub(u2, w2));
+    if (u.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    const int B = u.batch;
+    ctr.hmult += B;
+    ctr.keyswitch += B;
+    ctr.rescale += B;
+    const size_t nn = n(), ell = u.limbs;
+    count_bytes(11.0 * ell + ks_units(ell), B);
+    auto d01m = I.alloc((size_t)B * 2 * ell * nn * 8), d2m = I.alloc((size_t)B * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    dev::ew_tensor_win(d01, d2, u.data, w.data, u2.data, w2.data, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    const bool fuse = I.ks_fuse(B);
+    auto extm = I.modup(d2, ell, B, ell * nn, fuse);
+    auto r = new_ct(u.level + 1, u.slots, I.P.delta[u.level + 1], ell - 1, B);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
+    return r;
+}
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {
     if (ps.empty()) throw std::invalid_argument("sub_plain_stacked: no plaintexts");
     if (a.batch != 1) throw std::invalid_argument("sub_plain_stacked: a must be one ciphertext");

@@ -381,6 +381,32 @@ class Engine {
     // the two above: a_sub null takes the constant
     CtPtr mul_pairs_left(const char *what, const Ciphertext &a, const Ciphertext *a_sub, double c, const Ciphertext &b,
                          int P);
+    // The sign arguments of the window sums (DirectSortN::windowSums, DESIGN.md
+    // §6.7): G = part_as.size() partition keys (1..3) against B shifted operands each
+    // (part_bs key-major) and an optional order key against order_bs (B of them), as
+    // one stack of (2 G + V) B members.  Members (2 g) B + i and (2 g + 1) B + i =
+    // add_const(sub(*part_as[g], *part_bs[g B + i]), +eps resp. -eps).  Behind them the
+    // order key's V B members: with ps, member 2 G B + i = add_plain(sub(*order_a,
+    // *order_bs[i]), *ps[i]) (V = 1); with order_lo, members 2 G B + i =
+    // add_const(sub(*order_a, .), +eps) and (2 G + 1) B + i = add_const(sub(*order_lo, .),
+    // -eps) (V = 2); otherwise member 2 G B + i = add_const(sub(*order_a, .), order_const)
+    // (V = 1); no order_a: V = 0.  Word for word, written by one launch
+    // (k_sub_window_stacked: each operand loaded once, a left operand's words once
+    // per tile of members).  sub_stacked's level rules: left operands (all at one
+    // level) below the operands are level-adjusted once, above them every member
+    // takes its own ops.  FHE_WIN_FUSED=0 (A/B): sub_stacked per side, then
+    // add_const in place resp. add_plain per member.
+    CtPtr sub_window_stacked(const std::vector<const Ciphertext *> &part_as,
+                             const std::vector<const Ciphertext *> &part_bs, const Ciphertext *order_a,
+                             const Ciphertext *order_lo, const std::vector<const Ciphertext *> &order_bs,
+                             const std::vector<const Plaintext *> &ps, double order_const, double eps);
+    // stacks of B members each, u and w at one level, u2 and w2 at one level: member
+    // z = mul(sub(member(u, z), member(w, z)), sub(member(u2, z), member(w2, z))) word for
+    // word.  With all four at one level it is one tensor pass that forms both
+    // differences as it loads them (k_tensor_win), then mul's relinearisation /
+    // rescale tail; with the pairs at two levels (mul would level-adjust one) or
+    // under FHE_WIN_FUSED=0 it is sub, sub and the product.
+    CtPtr mul_sub_sub(const Ciphertext &u, const Ciphertext &w, const Ciphertext &u2, const Ciphertext &w2);
     CtPtr sum_members(const Ciphertext &a);
     // acc[p] (+)= sum_z a[p B + z] for the `groups` groups of B = a.batch / groups
     // consecutive members, in one launch (k_sum_member_groups); an empty acc

@@ -17,6 +17,7 @@ COEFF_DIR = os.path.join(HERE, 'data')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'fhe_gpu.h')
 PS_SPLIT_ENGINE, PS_SPLIT_OPENFHE = 0, 1  # fhe_set_ps_split (include/fhe_gpu.h)
 RUN_ROWS, RUN_LE, RUN_LT, RUN_BETWEEN = range(4)  # fhe_direct_running_sum's modes (FHE_RUN_*)
+WIN_ROWS, WIN_LE, WIN_LT, WIN_BETWEEN, WIN_GROUP = range(5)  # fhe_direct_window_sum's modes (FHE_WIN_*)
 
 FHE_OK, FHE_EINVAL, FHE_ENOKEY, FHE_EDEPTH, FHE_EHIP, FHE_ENOMEM, FHE_EINTERNAL, FHE_ENOCOMM, FHE_EIO = range(9)
 NAF, BNAF, BINARY = 0, 1, 2
@@ -164,6 +165,14 @@ _SIGS = {
     'fhe_sub_lex_stacked': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int,
                                       C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p)]),
     'fhe_mul_lex': (C.c_int, [vp, vp, C.c_double, vp, vp, C.POINTER(C.c_void_p)]),
+    'fhe_direct_window_sum': (C.c_int, [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, vp, vp, vp,
+                                        C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_int, ip, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    'fhe_window_sum_levels': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip]),
+    'fhe_sub_window_stacked': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int,
+                                         vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double,
+                                         C.POINTER(C.c_void_p)]),
+    'fhe_mul_sub_sub': (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(C.c_void_p)]),
     'fhe_sort_hybrid': (C.c_int, [vp, vp, vp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, vp, vp, PP]),
     'fhe_hybrid_parameters': (C.c_int, [C.c_int, ip, ip, C.c_int]),
@@ -1013,6 +1022,66 @@ class Context:
         word for word, in one tensor pass where t, u and w share a level"""
         return self._new(lib().fhe_mul_lex, t.h, float(t_const), u.h, w.h)
 
+    def window_sum(self, part_left, part_right, cols, eps, N, rots, cfg, order_left=None, order_right=None,
+                   mode=WIN_GROUP, lo=None, count=False):
+        """Window sums (fhe_direct_window_sum): out[p] has N slots, slot e holds the sum
+        of cols[p] over the right rows j that agree with left row e on every partition
+        key (part_left[g]_e = part_right[g]_j, 1 to 3 keys; the same handles for a self
+        join) and that the order key selects: WIN_ROWS / WIN_LE / WIN_LT / WIN_BETWEEN
+        are running_sum's modes on (order_left, order_right, lo) inside the partition
+        -- SUM(v) OVER (PARTITION BY g ORDER BY t ...), the as-of join, the
+        per-partition sliding window -- and WIN_GROUP (no order key; at least two
+        partition keys) is GROUP BY a, b and the join on several keys.  count=True:
+        returns (outs, count), the number of selected right rows (ROW_NUMBER() under
+        WIN_ROWS).  running_sum's conditions hold for every key; levels are
+        window_sum_levels(key_level, len(part_left) + (mode != WIN_GROUP), cfg)."""
+        r = np.asarray(rots, dtype=np.int32)
+        cols, part_left, part_right = list(cols), list(part_left), list(part_right)
+        if len(part_left) != len(part_right):
+            raise ValueError('window_sum: one right partition key per left one')
+        h = lambda x: None if x is None else x.h
+        pl = (C.c_void_p * max(1, len(part_left)))(*[h(k) for k in part_left])
+        pr = (C.c_void_p * max(1, len(part_right)))(*[h(k) for k in part_right])
+        arr = (C.c_void_p * max(1, len(cols)))(*[h(c) for c in cols])
+        outs = (C.c_void_p * max(1, len(cols)))()
+        cnt = C.c_void_p()
+        _chk(lib().fhe_direct_window_sum(self.h, pl, pr, len(part_left), h(order_left), h(lo), h(order_right), arr,
+                                         len(cols), int(mode), float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2],
+                                         outs, C.byref(cnt) if count else None))
+        res = [Ct(self, outs[i]) for i in range(len(cols))]
+        return (res, Ct(self, cnt.value)) if count else res
+
+    @staticmethod
+    def window_sum_levels(key_level, nfactors, cfg):
+        return window_sum_levels(key_level, nfactors, cfg)
+
+    def sub_window_stacked(self, part_as, part_bs, eps, mode=WIN_GROUP, order_a=None, order_bs=None, order_lo=None,
+                           ps=None):
+        """fhe_sub_window_stacked: with G = len(part_as) partition keys and part_bs
+        key-major (G * count ciphertexts), members (2 g) count + i and (2 g + 1) count + i
+        are add_const(sub(part_as[g], part_bs[g count + i]), +eps / -eps); from member
+        2 G count on the order key's by mode: WIN_ROWS add_plain(sub(order_a,
+        order_bs[i]), ps[i]), WIN_LE / WIN_LT add_const(sub(order_a, order_bs[i]), +eps /
+        -eps), WIN_BETWEEN that with +eps, then add_const(sub(order_lo, order_bs[i]),
+        -eps); WIN_GROUP none; word for word"""
+        G = len(part_as)
+        if G == 0 or len(part_bs) % G:
+            raise ValueError('sub_window_stacked: one operand list per partition key')
+        count = len(part_bs) // G
+        if order_bs is not None and len(order_bs) != count:
+            raise ValueError('sub_window_stacked: one order operand per partition operand')
+        if ps is not None and len(ps) != count:
+            raise ValueError('sub_window_stacked: one plaintext per operand')
+        arr = lambda xs: None if xs is None else (C.c_void_p * max(1, len(xs)))(*[x.h for x in xs])
+        return self._new(lib().fhe_sub_window_stacked, arr(part_as), G, arr(part_bs), count, int(mode),
+                         None if order_a is None else order_a.h, None if order_lo is None else order_lo.h,
+                         arr(order_bs), arr(ps), float(eps))
+
+    def mul_sub_sub(self, u, w, u2, w2):
+        """member z = mul(sub(member(u, z), member(w, z)), sub(member(u2, z), member(w2, z)))
+        word for word, in one tensor pass where the four share a level"""
+        return self._new(lib().fhe_mul_sub_sub, u.h, w.h, u2.h, w2.h)
+
     def mul_columns(self, a, cols):
         """the stack a (B members) times each single ciphertext of cols: member
         p * B + z of the result is mul(member(a, z), cols[p]) word for word"""
@@ -1274,6 +1343,17 @@ def group_sum_levels(key_level, cfg):
     keys at key_level under the composite sign cfg = (n, dg, df)"""
     col, out = C.c_int(), C.c_int()
     rc = lib().fhe_group_sum_levels(int(key_level), cfg[0], cfg[1], cfg[2], C.byref(col), C.byref(out))
+    if rc != FHE_OK:
+        raise FheError(rc, lib().fhe_last_error().decode())
+    return col.value, out.value
+
+
+def window_sum_levels(key_level, nfactors, cfg):
+    """fhe_window_sum_levels (pure host): (col_max_level, out_level) of window_sum for
+    keys at key_level and nfactors factors (the partition keys, plus one for an
+    order key) under the composite sign cfg = (n, dg, df)"""
+    col, out = C.c_int(), C.c_int()
+    rc = lib().fhe_window_sum_levels(int(key_level), int(nfactors), cfg[0], cfg[1], cfg[2], C.byref(col), C.byref(out))
     if rc != FHE_OK:
         raise FheError(rc, lib().fhe_last_error().decode())
     return col.value, out.value

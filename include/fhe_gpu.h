@@ -573,6 +573,89 @@ int fhe_sub_lex_stacked(fhe_ctx *ctx, const fhe_ct *const *as, int nkeys, const 
  * FHE_EINVAL for member counts or levels of u and w that do not fit. */
 int fhe_mul_lex(fhe_ctx *ctx, const fhe_ct *t, double t_const, const fhe_ct *u, const fhe_ct *w, fhe_ct **out);
 
+/* Window sums: add up columns over the right rows that agree with the left row on
+ * every partition key and that an order key selects (the project's own extension,
+ * like fhe_direct_select and the sums before it).  Every key and
+ * column holds N rows in N slots; all keys sit at one level.  With nparts
+ * partition keys (1..3), part_left[g] the left table's and part_right[g] the right
+ * table's (the same handle for a self join), outs[p] holds at slot e
+ *     sum_j c_ej cols[p]_j,   c_ej = prod_g [part_left[g]_e = part_right[g]_j] * r_ej,
+ * and *count_out (optional) sum_j c_ej.  A partition indicator is
+ * (sign(d + eps) - sign(d - eps)) / 2 for d = part_left[g]_e - part_right[g]_j; r_ej is
+ * fhe_direct_running_sum's weight for the mode on (order_left, order_lo,
+ * order_right) -- FHE_WIN_ROWS / LE / LT / BETWEEN have FHE_RUN_*'s values and
+ * meanings -- or 1 under FHE_WIN_GROUP, which takes no order key (every order_*
+ * NULL).  With F = nparts + (mode != FHE_WIN_GROUP) factors, 2 <= F <= 4; one
+ * partition key under FHE_WIN_GROUP is fhe_direct_group_sum and is refused.
+ *   SUM(v) OVER (PARTITION BY g ORDER BY t ROWS UNBOUNDED PRECEDING): nparts = 1,
+ *     FHE_WIN_ROWS, self join; its count is ROW_NUMBER(), LE's / LT's count + 1 RANK();
+ *   GROUP BY a, b and JOIN ON a.k1 = b.k1 AND a.k2 = b.k2: nparts = 2, FHE_WIN_GROUP;
+ *   the as-of join ON a.id = b.id AND b.t <= a.t: nparts = 1, FHE_WIN_LE;
+ *   PARTITION BY g ORDER BY t RANGE BETWEEN w PRECEDING AND w FOLLOWING: FHE_WIN_BETWEEN
+ *     with order_left = t + w and order_lo = t - w.
+ * The caller guarantees fhe_direct_running_sum's conditions on every key: 0 < eps <
+ * 0.5; equal values agree far below eps; distinct values, bounds included, differ
+ * by at least 2 eps; every sign argument has magnitude <= 1, for pairs of rows from
+ * different partitions too; the sign configuration resolves eps.  Levels
+ * (fhe_window_sum_levels): the sign outputs sit at L_m = key level + 1 + sign depth,
+ * their product after ceil(log2 F) levels at L_a; a column may sit at col_max_level
+ * = L_a - 2 at most and every output ends at out_level = L_a + 1.  The batches run
+ * stacked in chunks of fhe_set_sort_stack / (2 nparts + V) (V = 0, 1 or 2 sign
+ * members for the order key) on fhe_set_sort_lanes lanes, the columns in groups
+ * bounded by fhe_set_sort_column_members; the result does not depend on any of
+ * them, nor on fhe_set_mask_cache.  Unsharded.  fhe_set_sort_tiebreak has no effect
+ * here.  FHE_WIN_FUSED=0, read once per process, takes the unfused forms of the
+ * two entries below; same words.  FHE_EINVAL for nparts outside 1..3, F outside
+ * 2..4, a mode outside 0..4, an order key under FHE_WIN_GROUP or a missing one
+ * otherwise, order_lo outside FHE_WIN_BETWEEN or missing in it, a null handle, a
+ * stack, keys at different levels or with a slot count other than N, a column with
+ * another slot count, ncols < 0, nothing asked for, and eps outside (0, 0.5);
+ * FHE_EDEPTH, before any work, for a column above col_max_level and for a context
+ * without out_level levels.  On failure no output handle is set (every one is NULL). */
+#define FHE_WIN_ROWS 0
+#define FHE_WIN_LE 1
+#define FHE_WIN_LT 2
+#define FHE_WIN_BETWEEN 3
+#define FHE_WIN_GROUP 4
+int fhe_direct_window_sum(fhe_ctx *ctx, const fhe_ct *const *part_left, const fhe_ct *const *part_right, int nparts,
+                          const fhe_ct *order_left /* NULL under GROUP */, const fhe_ct *order_lo /* BETWEEN only */,
+                          const fhe_ct *order_right /* NULL under GROUP */, const fhe_ct *const *cols, int ncols,
+                          int mode, double eps, int N, const int32_t *rots, int nrot, int n, int dg, int df,
+                          fhe_ct **outs /* ncols handles */, fhe_ct **count_out /* may be NULL */);
+/* pure host: col_max_level and out_level above for keys at key_level and nfactors
+ * factors (2..4) under the composite sign (n, dg, df), n = 3 or 4.  Either pointer
+ * may be NULL.  FHE_EINVAL for nfactors outside 2..4, a negative level or degree, or
+ * another n. */
+int fhe_window_sum_levels(int key_level, int nfactors, int n, int dg, int df, int *col_max_level, int *out_level);
+/* for tests and bindings: the sign arguments of nparts partition keys (1..3) against
+ * count shifted copies each (part_bs key-major: part_bs[g count + i]) and, unless mode
+ * is FHE_WIN_GROUP, of an order key against order_bs (count of them), as one stack.
+ * Members (2 g) count + i and (2 g + 1) count + i = fhe_add_const(fhe_sub(part_as[g],
+ * part_bs[g count + i]), +eps resp. -eps).  Behind them, from member 2 nparts count on:
+ * FHE_WIN_ROWS count members fhe_add_plain(fhe_sub(order_a, order_bs[i]), ps[i]);
+ * FHE_WIN_LE / LT count members fhe_add_const(fhe_sub(order_a, order_bs[i]), +eps /
+ * -eps); FHE_WIN_BETWEEN count members fhe_add_const(fhe_sub(order_a, order_bs[i]), +eps),
+ * then count members fhe_add_const(fhe_sub(order_lo, order_bs[i]), -eps).  Word for
+ * word, written by one kernel that loads every operand once and a left operand once
+ * per four members (FHE_WIN_FUSED=0, read once per process: the stacked differences
+ * per side, then the constant in place or the plaintext per member).  Every left
+ * operand shares one level and so do the right ones; left operands at a lower level
+ * are level-adjusted once, at a higher one every member takes its own operations.
+ * order_lo goes with FHE_WIN_BETWEEN alone, ps (count plaintexts at the differences'
+ * level) with FHE_WIN_ROWS alone.  FHE_EINVAL for counts, modes or levels that do
+ * not fit. */
+int fhe_sub_window_stacked(fhe_ctx *ctx, const fhe_ct *const *part_as, int nparts, const fhe_ct *const *part_bs,
+                           int count, int mode, const fhe_ct *order_a, const fhe_ct *order_lo,
+                           const fhe_ct *const *order_bs, const fhe_pt *const *ps, double eps, fhe_ct **out);
+/* and the product of two indicators: u, w, u2 and w2 are stacks of B members, u and w
+ * at one level, u2 and w2 at one level; member z of the result =
+ * fhe_mul_relin(fhe_sub(u_z, w_z), fhe_sub(u2_z, w2_z)) word for word.  With all four at
+ * one level it is one tensor pass that forms both differences as it loads them and
+ * writes neither, then the product's relinearisation and rescale; with the pairs at
+ * two levels, or under FHE_WIN_FUSED=0, the differences are formed first and the
+ * product follows.  FHE_EINVAL for member counts or levels that do not fit. */
+int fhe_mul_sub_sub(fhe_ctx *ctx, const fhe_ct *u, const fhe_ct *w, const fhe_ct *u2, const fhe_ct *w2, fhe_ct **out);
+
 /* how many of a rank's sort batches run stacked through one compare / one
  * sinc PS (default 32: every launch then carries up to 32 ciphertexts; HBM use
  * grows with it).  Results do not depend on it. */
