@@ -1696,6 +1696,25 @@ int fhe_modup(fhe_ctx *ctx, const uint64_t *d, int ell, uint64_t *ext) {
 int fhe_moddown(fhe_ctx *ctx, const uint64_t *in, int ell, uint64_t *out) {
     return guard([&] { ctx->eng->moddown_host(in, (size_t)ell, out); });
 }
+int fhe_linear_sums_raw(fhe_ctx *ctx, const fhe_ct *const *xs, int m, const int64_t *K, const uint8_t *sh, int G,
+                        const int64_t *Kc, const uint8_t *shc, int level, fhe_ct **outs) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(xs);
+        NEED(K);
+        NEED(sh);
+        NEED(outs);
+        if (m < 1 || G < 1) throw std::invalid_argument("fhe_linear_sums_raw: m and G must be positive");
+        if ((Kc == nullptr) != (shc == nullptr)) throw std::invalid_argument("fhe_linear_sums_raw: Kc and shc go together");
+        std::vector<const Ciphertext *> v;
+        for (int i = 0; i < m; ++i) {
+            NEED(xs[i]);
+            v.push_back(xs[i]->p.get());
+        }
+        auto r = ctx->eng->linear_sums_raw(v, K, sh, (size_t)G, Kc, shc, level);
+        for (int g = 0; g < G; ++g) outs[g] = wrap(r[g]);
+    });
+}
 int fhe_automorph(fhe_ctx *ctx, const uint64_t *in, int limbs, uint64_t g, uint64_t *out) {
     return guard([&] { ctx->eng->automorph_host(in, (size_t)limbs, g, out); });
 }

@@ -605,7 +605,7 @@ __global__ __launch_bounds__(NT) void k_linear_sum_multi(MultiLinArgs A, size_t 
 //   * the K index runs over (source i, byte a) and the M index over (output t,
 //     shift s = a + c'), with A[(t, s), (i, a)] = e_{s-a}(c_{t,i}), so row s of
 //     output t accumulates sum_{i, a} s_{i,a} e_{s-a} exactly in int32 (at most
-//     256 terms of magnitude <= 2^14 per row);
+//     8 m terms of magnitude <= 2^14 per row, m <= LEAF_M = 64 sources);
 //   * out_t = sum_s v_s 256^s + C0 sum_i c_{t,i}: sixteen int32 rows combined
 //     into a signed 128-bit value (|value| < 32 * 2^120) and reduced once.
 // Rows are ordered so that one lane holds all sixteen shifts of one output: a
@@ -638,10 +638,15 @@ __device__ __forceinline__ u64 shift_window(u64 e, int s) {
     if (s <= 7) return r >> (8 * (7 - s));
     return s == 15 ? 0 : r << (8 * (s - 7));
 }
-// sum_{kk, r} v[kk][r] 256^(4 kk + r) + 2^126, reduced mod q.  |v| < 2^22, so
-// v0 + 256 v1 fits an int32 and each four-row group L_kk an int64 (< 2^47); the
-// signed 128-bit sum (|sum| < 2^125) is biased by 2^126 so the reduction sees
-// a non-negative value -- the caller's per-output constant takes 2^126 off again.
+// sum_{kk, r} v[kk][r] 256^(4 kk + r) + 2^126, reduced mod q.  A row is below
+// 7 * 2^14 m (m <= LEAF_M = 64 sources: < 2^23), so the naive bound of
+// v0 + 256 v1 does not fit an int32; the pair does, because byte 7 of a residue
+// is at most 15 and the top balanced digit of a constant lies in [0, 16]:
+// |v_s + 256 v_{s+1}| <= 26,296,320 m (worst at s = 6; tests/bigint_model.py
+// budget_bound_window derives it), 1,682,964,480 < 2^31 at m = 64 and in range
+// up to m = 81.  Each four-row group L_kk is an int64 (< 2^47); the signed
+// 128-bit sum (|sum| < 2^125) is biased by 2^126 so the reduction sees a
+// non-negative value -- the caller's per-output constant takes 2^126 off again.
 __device__ __forceinline__ u64 combine_rows(const v4i (&v)[4], const Mod &m) {
     int64_t L[4];
 #pragma unroll
@@ -888,7 +893,12 @@ __global__ __launch_bounds__(LF_NT) __attribute__((amdgpu_waves_per_eu(FHE_LF_WP
 // once ([group][row block][source step][lane] x 16 B, 14 KB per group at 56 sources)
 // and keeps it in LDS; every wave streams four 16-coefficient column tiles per
 // step with its B fragments in registers, so an A fragment read serves four MFMAs.
-// Rows: |v_b| < 448 * 2^14, so V = L0 + 2^32 L1 (L = four rows, < 2^47) -- one
+// Rows: |v_b| <= (7 * 2^14 + 15 * 128) m = 116,608 m for b < 7 and 14,576 m for
+// b = 7 (byte 7 of y is at most 15, digit 7 of d lies in [0, 16]), so the int32
+// pair v_b + 256 v_{b+1} is at most 257 * 116,608 m = 29,968,256 m: 1,917,968,384
+// < 2^31 at m = LEAF_M = 64, in range up to m = 71 and out of it from m = 72
+// (tests/bigint_model.py budget_bound_fold) -- this kernel is what bounds LEAF_M.
+// V = L0 + 2^32 L1 (L = four rows, < 2^47) -- one
 // 128-bit fold (combine_rows_add's two-term Shoup step, bias 2^126) per output.
 // Byte 0..6 of y are read as signed (u - 128), so out = V + 128 sum_{i, a<7} d.
 // Same residues as k_leaf_sums_mfma (exact integer sums, canonical results).

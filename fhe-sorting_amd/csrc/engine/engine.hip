@@ -2394,41 +2394,75 @@ std::vector<CtPtr> Engine::linear_sums_to(const std::vector<const Ciphertext *> 
     if (xs.empty()) throw std::invalid_argument("linear_sums_to: no inputs");
     if (consts && !rescale) throw std::invalid_argument("linear_sums_to: constants go with rescaled sums only");
     if (consts && consts->size() != c.size()) throw std::invalid_argument("linear_sums_to: one constant per output");
+    const int B = xs[0]->batch;
+    const size_t ell = I.P.limbs_at(target - 1), m = xs.size(), G = c.size();
+    const u64 qd = I.P.primes[I.P.L - target + 1];
+    count_bytes((2.0 * ell * m + 2.0 * ell) * G, B);  // op model: one linear sum per output
+    // the doubles as (K, sh) pairs: K 2^sh at the scale each input needs to reach the target's
+    std::vector<int64_t> K(G * m), Kc(consts ? G : 0);
+    std::vector<uint8_t> sh(G * m), shc(consts ? G : 0);
+    for (size_t g = 0; g < G && consts; ++g) {
+        const double cg = (*consts)[g];
+        const host::SConst k = cg != 0.0 ? host::const_at_scale(cg, I.P.delta[target]) : host::SConst{};
+        Kc[g] = k.k;
+        shc[g] = (uint8_t)k.sh;
+        if (cg != 0.0) count_bytes(4.0 * (ell - 1), B);  // the add_const copy it replaces
+    }
+    for (size_t g = 0; g < G; ++g) {
+        if (c[g].size() != m) throw std::invalid_argument("linear_sums_to: coefficient row size");
+        for (size_t i = 0; i < m; ++i) {
+            const host::SConst k = host::const_to_target(c[g][i], I.P.delta[target], qd, xs[i]->scale);
+            K[g * m + i] = k.k;
+            sh[g * m + i] = (uint8_t)k.sh;
+        }
+    }
+    return linear_sums_run(xs, K.data(), sh.data(), consts ? Kc.data() : nullptr, consts ? shc.data() : nullptr, G,
+                           target, rescale, "linear_sums_to");
+}
+
+std::vector<CtPtr> Engine::linear_sums_raw(const std::vector<const Ciphertext *> &xs, const int64_t *K,
+                                           const uint8_t *sh, size_t G, const int64_t *Kc, const uint8_t *shc,
+                                           int level) {
+    auto &I = *impl;
+    if (level < 0 || level >= I.P.L) throw std::invalid_argument("linear_sums_raw: level out of range");
+    if (xs.empty() || G == 0) throw std::invalid_argument("linear_sums_raw: no inputs or no outputs");
+    if (!K || !sh || (Kc && !shc)) throw std::invalid_argument("linear_sums_raw: null table");
+    const int64_t lim = (int64_t)1 << 62;
+    for (size_t t = 0; t < G * xs.size(); ++t)
+        if (K[t] > lim || K[t] < -lim) throw std::invalid_argument("linear_sums_raw: |K| above 2^62");
+    for (size_t g = 0; g < G && Kc; ++g)
+        if (Kc[g] > lim || Kc[g] < -lim) throw std::invalid_argument("linear_sums_raw: |K| above 2^62");
+    return linear_sums_run(xs, K, sh, Kc, shc, G, level + 1, false, "linear_sums_raw");
+}
+
+// linear_sums_to behind the doubles: K, sh [G][m], Kc, shc [G] or null
+std::vector<CtPtr> Engine::linear_sums_run(const std::vector<const Ciphertext *> &xs, const int64_t *Kall,
+                                           const uint8_t *shall, const int64_t *Kc, const uint8_t *shc, size_t Gall,
+                                           int target, bool rescale, const char *who) {
+    auto &I = *impl;
     const int B = xs[0]->batch, segs = 2 * B;
     const size_t nn = n(), ell = I.P.limbs_at(target - 1), m = xs.size();
     const u64 qd = I.P.primes[I.P.L - target + 1];
-    count_bytes((2.0 * ell * m + 2.0 * ell) * c.size(), B);  // op model: one linear sum per output
     std::vector<const u64 *> xp(m);
     std::vector<size_t> xseg(m);
     for (size_t i = 0; i < m; ++i) {
-        if (xs[i]->level > target - 1) throw std::invalid_argument("linear_sums_to: input level too high");
-        if (xs[i]->batch != B) throw std::invalid_argument("linear_sums_to: batch size mismatch");
+        if (xs[i]->level > target - 1) throw std::invalid_argument(std::string(who) + ": input level too high");
+        if (xs[i]->batch != B) throw std::invalid_argument(std::string(who) + ": batch size mismatch");
         xp[i] = xs[i]->data;
         xseg[i] = xs[i]->limbs * nn;
     }
     std::vector<CtPtr> outs;
     // passes of at most LEAF_G = 32 outputs (the kernel's limit), balanced: 36 -> 18 + 18
-    const size_t passes = (c.size() + dev::LEAF_G - 1) / dev::LEAF_G, per = (c.size() + passes - 1) / passes;
+    const size_t passes = (Gall + dev::LEAF_G - 1) / dev::LEAF_G, per = (Gall + passes - 1) / passes;
     const bool mfma = dev::linear_sums_on_mfma(LOGN) && m <= (size_t)dev::LEAF_M;
-    for (size_t g0 = 0; g0 < c.size(); g0 += per) {
-        const int G = (int)std::min<size_t>(per, c.size() - g0);
+    for (size_t g0 = 0; g0 < Gall; g0 += per) {
+        const int G = (int)std::min<size_t>(per, Gall - g0);
         // (with constants: G more entries behind the [G][m] rows, ew_linear_sum_multi's cfold)
-        std::vector<int64_t> K((size_t)G * m + (consts ? G : 0));
-        std::vector<uint8_t> sh((size_t)G * m + (consts ? G : 0));
-        for (int g = 0; g < G && consts; ++g) {
-            const double cg = (*consts)[g0 + g];
-            const host::SConst k = cg != 0.0 ? host::const_at_scale(cg, I.P.delta[target]) : host::SConst{};
-            K[(size_t)G * m + g] = k.k;
-            sh[(size_t)G * m + g] = (uint8_t)k.sh;
-            if (cg != 0.0) count_bytes(4.0 * (ell - 1), B);  // the add_const copy it replaces
-        }
-        for (int g = 0; g < G; ++g) {
-            if (c[g0 + g].size() != m) throw std::invalid_argument("linear_sums_to: coefficient row size");
-            for (size_t i = 0; i < m; ++i) {
-                const host::SConst k = host::const_to_target(c[g0 + g][i], I.P.delta[target], qd, xs[i]->scale);
-                K[(size_t)g * m + i] = k.k;
-                sh[(size_t)g * m + i] = (uint8_t)k.sh;
-            }
+        std::vector<int64_t> K(Kall + g0 * m, Kall + (g0 + G) * m);
+        std::vector<uint8_t> sh(shall + g0 * m, shall + (g0 + G) * m);
+        if (Kc) {
+            K.insert(K.end(), Kc + g0, Kc + g0 + G);
+            sh.insert(sh.end(), shc + g0, shc + g0 + G);
         }
         auto tm = I.alloc((size_t)G * segs * ell * nn * 8);
         u64 *t = static_cast<u64 *>(tm->p);
@@ -2437,7 +2471,7 @@ std::vector<CtPtr> Engine::linear_sums_to(const std::vector<const Ciphertext *> 
         std::pair<const int64_t *, const uint8_t *> dk{nullptr, nullptr};
         if (mfma) dk = I.const_table(K, sh);
         dev::ew_linear_sum_multi(op.data(), G, xp.data(), xseg.data(), K.data(), (int)m, (int)ell, segs, ell * nn,
-                                 MODS, LOGN, ST, sh.data(), dk.first, dk.second, consts ? (int)ell - 1 : 0, qd);
+                                 MODS, LOGN, ST, sh.data(), dk.first, dk.second, Kc ? (int)ell - 1 : 0, qd);
         if (!rescale) {  // raw sums at the pre-rescale scale, views into one allocation
             for (int g = 0; g < G; ++g) {
                 auto r = std::make_shared<Ciphertext>();

@@ -311,6 +311,13 @@ class Engine {
     std::vector<CtPtr> linear_sums_to(const std::vector<const Ciphertext *> &xs,
                                       const std::vector<std::vector<double>> &c, int target, bool rescale = true,
                                       const std::vector<double> *consts = nullptr);
+    // linear_sums_to behind its doubles (a device-level test hook): the constants
+    // as the pairs (K, sh) the kernels take, K [G][m] with |K| <= 2^62 standing for
+    // K 2^sh, Kc / shc [G] or null the folded constants.  G unrescaled sums at
+    // `level` through the same tables, launches and passes as linear_sums_to
+    // (with Kc: + Kc 2^shc q_last on c0 below the last limb)
+    std::vector<CtPtr> linear_sums_raw(const std::vector<const Ciphertext *> &xs, const int64_t *K, const uint8_t *sh,
+                                       size_t G, const int64_t *Kc, const uint8_t *shc, int level);
     CtPtr trivial_const(double c, int level, int slots, int batch = 1);
     CtPtr zero_like(int level, int slots, int batch = 1);
     // batches: stack (copies; equal levels), member view (no copy), member sum
@@ -472,6 +479,9 @@ class Engine {
   private:
     std::shared_ptr<int> ps_split_ = std::make_shared<int>(PS_SPLIT_OPENFHE);
     CtPtr new_ct(int level, int slots, double scale, size_t limbs, int batch = 1);
+    std::vector<CtPtr> linear_sums_run(const std::vector<const Ciphertext *> &xs, const int64_t *K, const uint8_t *sh,
+                                       const int64_t *Kc, const uint8_t *shc, size_t G, int target, bool rescale,
+                                       const char *who);
 };
 
 // Raised on a rotation index with no key (the reference's OpenFHE raises on

@@ -212,6 +212,9 @@ _SIGS = {
     'fhe_modup': (C.c_int, [vp, u64p, C.c_int, u64p]),
     'fhe_moddown': (C.c_int, [vp, u64p, C.c_int, u64p]),
     'fhe_automorph': (C.c_int, [vp, u64p, C.c_int, C.c_uint64, u64p]),
+    'fhe_linear_sums_raw': (C.c_int, [vp, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_uint8),
+                                      C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.c_int,
+                                      C.POINTER(C.c_void_p)]),
     'fhe_counters': (C.c_int, [vp, u64p]),
     'fhe_collective_stats': (C.c_int, [vp, u64p]),
     'fhe_boot_counters': (C.c_int, [vp, u64p]),
@@ -1222,6 +1225,29 @@ class Context:
         out = np.empty((ell, self.n), dtype=np.uint64)
         _chk(lib().fhe_moddown(self.h, _u64(x), ell, _u64(out)))
         return out
+
+    def linear_sums_raw(self, xs, K, sh, level, consts=None):
+        """the multi-output sums of products behind linear_sums_to's doubles: K, sh
+        [G][m] integers (the constant K 2^sh, |K| <= 2^62), consts = (Kc, shc) of [G]
+        or None; G unrescaled sums at `level` (fhe_linear_sums_raw)"""
+        K = np.ascontiguousarray(K, dtype=np.int64)
+        sh = np.ascontiguousarray(sh, dtype=np.uint8)
+        G, m = K.shape
+        if sh.shape != K.shape or m != len(xs):
+            raise ValueError('linear_sums_raw: K and sh are [G][len(xs)]')
+        i64p, u8p = C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+        kc = sc = None
+        if consts is not None:
+            kc = np.ascontiguousarray(consts[0], dtype=np.int64)
+            sc = np.ascontiguousarray(consts[1], dtype=np.uint8)
+            if kc.shape != (G,) or sc.shape != (G,):
+                raise ValueError('linear_sums_raw: one folded constant per output')
+        arr = (C.c_void_p * m)(*[x.h for x in xs])
+        outs = (C.c_void_p * G)()
+        _chk(lib().fhe_linear_sums_raw(self.h, arr, m, K.ctypes.data_as(i64p), sh.ctypes.data_as(u8p), G,
+                                       None if kc is None else kc.ctypes.data_as(i64p),
+                                       None if sc is None else sc.ctypes.data_as(u8p), level, outs))
+        return [Ct(self, outs[g]) for g in range(G)]
 
     def automorph(self, x, g):
         x = np.ascontiguousarray(x, dtype=np.uint64)

@@ -846,6 +846,15 @@ int fhe_ntt(fhe_ctx *ctx, uint64_t *host, int prime_index, int limbs, int invers
 int fhe_modup(fhe_ctx *ctx, const uint64_t *d, int ell, uint64_t *ext);
 int fhe_moddown(fhe_ctx *ctx, const uint64_t *in, int ell, uint64_t *out);
 int fhe_automorph(fhe_ctx *ctx, const uint64_t *in, int limbs, uint64_t galois, uint64_t *out);
+/* kernel-level parity of the multi-output sums of products (the Paterson-Stockmeyer leaves):
+ * outs[g] = sum_i (K[g m + i] 2^sh[g m + i] mod q_l) xs[i], g < G, unrescaled at `level`, with the
+ * constants as the integer pairs the kernels take instead of doubles (|K| <= 2^62, else
+ * FHE_EINVAL).  Kc / shc ([G], or both NULL): + (Kc[g] 2^shc[g]) q_last mod q_l on c0 below the
+ * last limb, the constant a following rescale turns into + Kc 2^shc.  Inputs above `level` or of
+ * mixed batch sizes are refused.  Same tables, kernel selection and passes as the sums inside
+ * fhe_cheb_ps. */
+int fhe_linear_sums_raw(fhe_ctx *ctx, const fhe_ct *const *xs, int m, const int64_t *K, const uint8_t *sh, int G,
+                        const int64_t *Kc, const uint8_t *shc, int level, fhe_ct **outs);
 /* kernel-level parity: a_digit of key `kid` over all nq+K primes, [nall][n] to host */
 int fhe_public_poly(fhe_ctx *ctx, const uint8_t seed[32], uint64_t kid, int digit, uint64_t *out);
 /* Device-memory variants (SURVEY §8(b) fhe_ntt_fwd/inv, fhe_automorph): the

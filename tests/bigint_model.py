@@ -58,7 +58,21 @@ either way, |X_P / P - 1/2| <= eps, i.e. with the distance written as
 candidate c -+ P is correct as well; moddown() returns the tie indices and the
 other candidate's coefficients.  The compare is done in integers:
 |2 X_P - P| 2^53 <= (K^2 + 11 K) P.
+
+Constants and their sums (second half of the file).  A real constant is
+the pair (k, sh) standing for k 2^sh (scaled_const and its two callers);
+linear_sums / mul_plain_sum_words are the sums of products over the
+integers, reduced once; add_const, mul_const, mul_const_to, mul_int,
+level_adjust, linear_sum_to, mul_plain_sum (batches, groups) and
+mul_add_const are Model methods defined from those and from rescale / the
+key switch above.  The last section restates how the matrix-core kernels
+split such a sum into int32 rows of signed bytes times balanced digits
+(rows_window, rows_fold), only to choose inputs (target_words) and to bound
+the rows (budget_bound_window, budget_bound_fold); split30_middle does the
+same for the VALU form's 30-bit halves.
 """
+import math
+
 import numpy as np
 
 
@@ -536,3 +550,366 @@ def check_mul_noise(model, a, b, out, s):
     assert worst * 2 * den <= 2 * num + (1 + h) * ql * den, \
         f'product noise 2^{bits(worst // ql):.1f} above the bound 2^{bits((2 * num + (1 + h) * ql * den) // (2 * den * ql)):.1f}'
     return bits(worst // ql), bits((2 * num + (1 + h) * ql * den) // (2 * den * ql))
+
+
+# ============================================================================
+# Constants, and sums of products of ciphertext words with constants
+# ============================================================================
+# A real constant x enters the arithmetic as the integer pair (k, sh) standing
+# for k 2^sh ("constants carried as k 2^sh"): x itself rounded
+# half away from zero while |x| <= 2^62, else the 62 leading bits of x and a
+# shift.  Everything downstream is integer: the residue (k 2^sh) mod q
+# multiplies words, sums are taken over the integers and reduced once.
+def round_half_away(x):
+    """the nearest integer to the double x, ties away from zero (exact: through
+    the double's integer ratio, no floating-point add)"""
+    num, den = float(x).as_integer_ratio()
+    r = (2 * abs(num) + den) // (2 * den)
+    return r if num >= 0 else -r
+
+
+def scaled_const(x):
+    """x -> (k, sh): (round(x), 0) if |x| <= 2^62; else sh = ceil(log2 |x|) - 62
+    (log2 evaluated in doubles, as the specification states it) and
+    k = round(x / 2^sh), the division by a power of two being exact"""
+    x = float(x)
+    if not np.isfinite(x):
+        raise ValueError('scaled constant is not finite')
+    if abs(x) <= 2.0 ** 62:
+        return round_half_away(x), 0
+    sh =math.ceil(math.log2(abs(x))) - 62
+    return round_half_away(math.ldexp(x, -sh)), sh
+
+
+def const_at_scale(c, scale):
+    return scaled_const(float(c) * float(scale))
+
+
+def const_to_target(c, delta_t, q_dropped, scale_in):
+    """the constant that takes an input at scale_in to delta_t after the
+    rescale by q_dropped: doubles, left to right"""
+    return scaled_const(float(c) * float(delta_t) * float(int(q_dropped)) / float(scale_in))
+
+
+def const_residue(k, sh, q):
+    return (int(k) * 2 ** int(sh)) % int(q)
+
+
+def linear_sums(xs, K, sh, primes, consts=None):
+    """out_g[p][l] = sum_i residue(K[g][i], sh[g][i]; q_l) x_i[p][l] mod q_l over
+    the ell = len(primes) limbs; an input with more limbs contributes its
+    first ell.  consts = (Kc, shc): + residue(Kc[g]) q_{ell-1} mod q_l on c0
+    (p = 0) for l < ell - 1; the last limb is left as it is.
+    xs: [2][limbs_i][n] words each; returns G arrays [2][ell][n] (uint64)."""
+    ell, G, m = len(primes), len(K), len(xs)
+    n = np.asarray(xs[0]).shape[-1]
+    out = [np.empty((2, ell, n), dtype=np.uint64) for _ in range(G)]
+    for l, q in enumerate(int(p) for p in primes):
+        W = np.array([[const_residue(K[g][i], sh[g][i], q) for i in range(m)] for g in range(G)], dtype=object)
+        X = np.stack([obj(np.asarray(x)[:, l, :]).reshape(2 * n) for x in xs])  # [m][2 n]
+        S = W.dot(X)  # exact integers
+        for g in range(G):
+            s = S[g].reshape(2, n)
+            if consts is not None and l < ell - 1:
+                s[0] = s[0] + const_residue(consts[0][g], consts[1][g], q) * int(primes[ell - 1])
+            out[g][:, l, :] = u64(s % q)
+    return out
+
+
+def mul_plain_sum_words(cts, pts, primes):
+    """sum_i ct_i pt_i over the limbs of `primes`, unrescaled: cts [2][ell][n], pts [ell][n]"""
+    ell = len(primes)
+    n = np.asarray(cts[0]).shape[-1]
+    out = np.empty((2, ell, n), dtype=np.uint64)
+    for l, q in enumerate(int(p) for p in primes):
+        for h in range(2):
+            s = 0
+            for c, p in zip(cts, pts):
+                s = s + obj(c[h][l]) * obj(p[l])
+            out[h, l] = u64(s % q)
+    return out
+
+
+def _add_ops(cls):
+    """the constant ops of the engine's surface as Model methods; every scale is
+    an argument (a double), every ciphertext [2][limbs][n] words"""
+    def ell_of(self, level):
+        return self.nq - level
+
+    def add_const(self, ct, c, scale):
+        """c at the ciphertext's scale joins c0 on every limb"""
+        k, sh = const_at_scale(c, scale)
+        out = np.array(ct, dtype=np.uint64)
+        for l in range(out.shape[1]):
+            out[0, l] = u64((obj(ct[0][l]) + const_residue(k, sh, self.q[l])) % self.q[l])
+        return out
+
+    def mul_int(self, ct, k):
+        return np.stack([self._limbwise(lambda i: obj(ct[h][i]) * int(k), np.asarray(ct).shape[1]) for h in range(2)])
+
+    def mul_const_to(self, ct, c, scale_in, target, delta):
+        """the first ell = limbs(target - 1) limbs times the constant that lands
+        the product at delta[target], then the rescale"""
+        ell = self.ell_of(target - 1)
+        k, sh = const_to_target(c, delta[target], self.q[ell - 1], scale_in)
+        prod = np.stack([self._limbwise(lambda i: obj(ct[h][i]) * const_residue(k, sh, self.q[i]), ell)
+                         for h in range(2)])
+        return self.rescale(prod)
+
+    def mul_const(self, ct, c, scale_in, level, delta):
+        return self.mul_const_to(ct, c, scale_in, level + 1, delta)
+
+    def level_adjust(self, ct, scale_in, level, target, delta):
+        """the product with 1.0 to the target level; the identity at its own level"""
+        if target == level:
+            return np.array(ct, dtype=np.uint64)
+        return self.mul_const_to(ct, 1.0, scale_in, target, delta)
+
+    def linear_sum_to(self, xs, cs, scales, target, delta):
+        ell = self.ell_of(target - 1)
+        ks = [const_to_target(c, delta[target], self.q[ell - 1], s) for c, s in zip(cs, scales)]
+        return self.rescale(linear_sums(xs, [[k for k, _ in ks]], [[s for _, s in ks]], self.q[:ell])[0])
+
+    def mul_plain_sum(self, cts, pts):
+        """sum_i ct_i pt_i, one rescale"""
+        return self.rescale(mul_plain_sum_words(cts, pts, self.q[:np.asarray(cts[0]).shape[1]]))
+
+    def mul_plain_sum_batches(self, cts, pts_per_batch):
+        """member b = mul_plain_sum(cts, pts_per_batch[b])"""
+        return [self.mul_plain_sum(cts, pts) for pts in pts_per_batch]
+
+    def mul_plain_sum_groups(self, members, pts, groups):
+        """member g = mul_plain_sum(members[g Z : (g + 1) Z], pts), Z = len(pts)"""
+        Z = len(pts)
+        return [self.mul_plain_sum(members[g * Z:(g + 1) * Z], pts) for g in range(groups)]
+
+    def mul_add_const(self, a, b, relin, level, scale_a, delta, xs=(), cs=(), scales=(), a_add=None, a_const=0.0,
+                      out_const=0.0, ks=None):
+        """(a [+ a_add] + a_const) b + sum_i cs_i xs_i + out_const with one
+        relinearisation and one rescale; a, b (and a_add) at `level`.  Returns
+        ([2][ell - 1][n], ModDown ties, ks); ks = keyswitch(d2) may be handed back
+        in for another call with the same (a + a_add)_1 b_1."""
+        ell = self.ell_of(level)
+        a = np.asarray(a)
+        left = np.array(a, dtype=np.uint64)
+        if a_add is not None:
+            left = np.stack([self._limbwise(lambda i: obj(a[h][i]) + obj(a_add[h][i]), ell) for h in range(2)])
+        if a_const != 0.0:
+            left = self.add_const(left, a_const, scale_a)
+        a0, a1, b0, b1 = obj(left[0]), obj(left[1]), obj(b[0]), obj(b[1])
+        d0 = self._limbwise(lambda i: a0[i] * b0[i], ell)
+        d1 = self._limbwise(lambda i: a0[i] * b1[i] + a1[i] * b0[i], ell)
+        d2 = self._limbwise(lambda i: a1[i] * b1[i], ell)
+        if len(xs):
+            kk = [const_to_target(c, delta[level + 1], self.q[ell - 1], s) for c, s in zip(cs, scales)]
+            lin = linear_sums(xs, [[k for k, _ in kk]], [[s for _, s in kk]], self.q[:ell])[0]
+            d0 = self._limbwise(lambda i: obj(d0[i]) + obj(lin[0][i]), ell)
+            d1 = self._limbwise(lambda i: obj(d1[i]) + obj(lin[1][i]), ell)
+        if out_const != 0.0:
+            k, sh = const_at_scale(out_const, delta[level + 1])
+            d0 = np.stack([u64((obj(d0[i]) + (const_residue(k, sh, self.q[i]) * self.q[ell - 1] if i < ell - 1 else 0))
+                               % self.q[i]) for i in range(ell)])
+        ks = ks if ks is not None else self.keyswitch(d2, relin)
+        t0 = self._limbwise(lambda i: obj(d0[i]) + obj(ks[0][0, i]), ell)
+        t1 = self._limbwise(lambda i: obj(d1[i]) + obj(ks[0][1, i]), ell)
+        return self.rescale(np.stack([t0, t1])), ks[1], ks
+
+    for f in (ell_of, add_const, mul_int, mul_const_to, mul_const, level_adjust, linear_sum_to, mul_plain_sum,
+              mul_plain_sum_batches, mul_plain_sum_groups, mul_add_const):
+        setattr(cls, f.__name__, f)
+
+
+_add_ops(Model)
+
+
+# ---------------------------------------------- the MFMA kernels' int32 rows ----
+# The matrix-core kernels form an exact sum of products from signed bytes:
+# a word y < q < 2^60 is read as the bytes u_0 .. u_7 (y = sum_a u_a 256^a), of
+# which bytes 0..6 are taken as s_a = u_a - 128 in [-128, 128) and byte 7 as
+# s_7 = u_7 in [0, 16); a constant c < q is written in balanced base-256
+# digits, c = sum_d e_d 256^d with e_d in [-128, 128).  For c < 2^60 the top
+# digit satisfies 0 <= e_7 <= 16: the seven lower digits sum to a value in
+# [-128, 127] (256^7 - 1)/255, of magnitude below 0.502 2^56, so
+# e_7 2^56 = c - (lower digits) lies in (-0.502 2^56, 16.502 2^56).
+#
+# The functions below restate the two decompositions.  They choose inputs and
+# account for the int32 budget; expected outputs always come from linear_sums.
+C0 = 0x0080808080808080  # sum_{a<7} 128 256^a: y = C0 + sum_a s_a 256^a
+
+
+def balanced_digits(c):
+    """the 8 balanced base-256 digits of 0 <= c < 2^60, least significant first"""
+    v, out = int(c), []
+    for _ in range(8):
+        d = v & 255
+        if d >= 128:
+            d -= 256
+        v = (v - d) >> 8
+        out.append(d)
+    assert v == 0 and sum(d << (8 * i) for i, d in enumerate(out)) == int(c)
+    return out
+
+
+def signed_bytes(ys):
+    """ys: integer array [...] of words < 2^60 -> int64 [8][...]: s_a"""
+    y = np.asarray(ys, dtype=np.uint64)
+    return np.stack([((y >> np.uint64(8 * a)) & np.uint64(255)).astype(np.int64) - (128 if a < 7 else 0) for a in range(8)])
+
+
+def _combined(rows):
+    return rows[0::2] + 256 * rows[1::2]
+
+
+def rows_window(residues, ys):
+    """The window kernel's rows for one output: residues c_i (m ints), ys [m][...]
+    words.  Row s (0..15) = sum_{i, a} s_{i,a} e_{s-a}(c_i); then
+    sum_s v_s 256^s + C0 sum_i c_i = sum_i c_i y_i over the integers.
+    Returns (rows [16][...], combined [8][...]) as int64, combined[j] =
+    v_{2j} + 256 v_{2j+1}: the words the kernel forms in int32."""
+    ys = np.asarray(ys, dtype=np.uint64)
+    rows = np.zeros((16,) + ys.shape[1:], dtype=np.int64)
+    for i, c in enumerate(residues):
+        e, s = balanced_digits(c), signed_bytes(ys[i])
+        for a in range(8):
+            for d in range(8):
+                if e[d]:
+                    rows[a + d] += s[a] * e[d]
+    return rows, _combined(rows)
+
+
+def rows_fold(residues, ys, q):
+    """The fold kernel's rows for one output: d_{i,a} = 256^a c_i mod q, row b
+    (0..7) = sum_{i, a} s_{i,a} e_b(d_{i,a}); then
+    sum_b v_b 256^b + 128 sum_{i, a<7} d_{i,a} = sum_i c_i y_i mod q.
+    Returns (rows [8][...], combined [4][...]) as int64."""
+    ys = np.asarray(ys, dtype=np.uint64)
+    rows = np.zeros((8,) + ys.shape[1:], dtype=np.int64)
+    for i, c in enumerate(residues):
+        s = signed_bytes(ys[i])
+        for a in range(8):
+            e = balanced_digits(int(c) * 256 ** a % int(q))
+            for b in range(8):
+                if e[b]:
+                    rows[b] += s[a] * e[b]
+    return rows, _combined(rows)
+
+
+def recombine_window(rows, residues):
+    """sum_s v_s 256^s + C0 sum c: the integer sum_i c_i y_i (object array)"""
+    return sum(obj(rows[s]) * 256 ** s for s in range(16)) + C0 * sum(int(c) for c in residues)
+
+
+def recombine_fold(rows, residues, q):
+    """sum_b v_b 256^b + 128 sum_{i, a<7} d_{i,a}, congruent to sum_i c_i y_i mod q"""
+    corr = 128 * sum(int(c) * 256 ** a % int(q) for c in residues for a in range(7))
+    return sum(obj(rows[b]) * 256 ** b for b in range(8)) + corr
+
+
+def digit_table(form, residues, q):
+    """int64 [m][8][8]: entry [i][a][b] = e_b(c_i) (window, the same for every
+    a) or e_b(256^a c_i mod q) (fold)"""
+    t = np.zeros((len(residues), 8, 8), dtype=np.int64)
+    for i, c in enumerate(residues):
+        for a in range(8):
+            t[i, a] = balanced_digits(c if form == 'window' else int(c) * 256 ** a % int(q))
+    return t
+
+
+def byte_weights(form, residues, q, pair, table=None):
+    """w[i][a]: the factor of s_{i,a} in the combined word `pair`
+    (v_{2 pair} + 256 v_{2 pair + 1}) of one output; form 'window' or 'fold'"""
+    t = digit_table(form, residues, q) if table is None else table
+    w = np.zeros((len(residues), 8), dtype=np.int64)
+    for a in range(8):
+        for row, f in ((2 * pair, 1), (2 * pair + 1, 256)):
+            d = row - a if form == 'window' else row
+            if 0 <= d < 8:
+                w[:, a] += f * t[:, a, d]
+    return w
+
+
+def extreme_word(w, sign, q):
+    """the word y < q whose signed bytes push sum_a s_a w[a] furthest in the
+    direction `sign`: from the top byte down, the largest byte the bound y <= q - 1
+    still allows where sign w[a] > 0, else 0 (0xFF / 0x00 once below the bound)"""
+    top = [((int(q) - 1) >> (8 * a)) & 255 for a in range(8)]
+    y, tight = 0, True
+    for a in range(7, -1, -1):
+        hi = top[a] if tight else 255
+        u = hi if sign * int(w[a]) > 0 else 0
+        tight = tight and u == top[a]
+        y |= u << (8 * a)
+    assert y < int(q)
+    return y
+
+
+def target_words(form, residues, q, n):
+    """[m][n] words below q for the sources of one limb; residues [G][m] are the
+    constants' residues at this limb.  Coefficient k aims at the triple
+    (output, pair, sign) number k mod (2 G P), P = 8 pairs (window) or 4 (fold):
+    every byte of every source is set by the sign of the factor it meets in that
+    combined word.  Returns (words, triples)."""
+    G, m = len(residues), len(residues[0])
+    P = 8 if form == 'window' else 4
+    triples = [(g, p, s) for g in range(G) for p in range(P) for s in (1, -1)]
+    cols, tables = [], {}
+    for g, p, s in triples[:n]:
+        if g not in tables:
+            tables[g] = digit_table(form, residues[g], q)
+        w = byte_weights(form, residues[g], q, p, tables[g])
+        cols.append([extreme_word(w[i], s, q) for i in range(m)])
+    out = np.empty((m, n), dtype=np.uint64)
+    for k in range(n):
+        out[:, k] = np.array(cols[k % len(cols)], dtype=np.uint64)
+    return out, triples
+
+
+def split30_middle(residues, ys):
+    """The VALU sums split words and constants into 30-bit halves and keep the
+    four partial sums of up to 16 terms in 64 bits each; the two middle ones
+    are added before they join the 128-bit total.  Returns the largest
+    s01 + s10 = sum_i lo(y_i) hi(c_i) + sum_i hi(y_i) lo(c_i) over the chunks of
+    16 sources (ys [m][...]), as Python ints: at 2^64 and above the addition
+    carries."""
+    M30 = (1 << 30) - 1
+    best = 0
+    for base in range(0, len(residues), 16):
+        mid = 0
+        for i in range(base, min(len(residues), base + 16)):
+            y, c = obj(ys[i]), int(residues[i])
+            s01, s10 = (y & M30) * (c >> 30), (y >> 30) * (c & M30)
+            mid = mid + s01 + s10
+        best = max(best, int(np.max(mid)))
+    return best
+
+
+# worst cases over every y < q < 2^60 and c < q: |s_a| <= S_a, |e_d| <= E_d
+_S = [128] * 7 + [15]
+_E = [128] * 7 + [16]
+
+
+def budget_bound_window(m):
+    """max |v_s + 256 v_{s+1}|, s even, of the window kernel with m sources.
+    v_s + 256 v_{s+1} = sum_i sum_a s_{i,a} (e_{s-a} + 256 e_{s+1-a}) (digits
+    outside 0..7 are zero), so by the triangle inequality one source adds at
+    most B_s = sum_a S_a (E_{s-a} + 256 E_{s+1-a}) with S = (128 x 7, 15) the
+    byte magnitudes and E = (128 x 7, 16) the digit magnitudes derived above.
+    The maximum over the even s is at s = 6: v_6 <= 7 2^14 = 114,688 and
+    v_7 <= 128 16 + 6 2^14 + 15 128 = 102,272, B_6 = 26,296,320.  The bound is
+    m B_6: 1,682,964,480 at m = 64, below 2^31 up to m = 81."""
+    def E(d):
+        return _E[d] if 0 <= d < 8 else 0
+    return m * max(sum(_S[a] * (E(s - a) + 256 * E(s + 1 - a)) for a in range(8)) for s in range(0, 16, 2))
+
+
+def budget_bound_fold(m):
+    """max |v_b + 256 v_{b+1}|, b even, of the fold kernel with m sources.  Row b
+    is sum_{i,a} s_{i,a} e_b(d_{i,a}) with d_{i,a} = 256^a c_i mod q any residue
+    below q, so the digits of different a are independent and one source adds
+    at most (sum_a S_a) E_b = 911 E_b to |v_b|: 116,608 for b < 7, 14,576 for
+    b = 7.  The pairs (0,1), (2,3), (4,5) reach 257 x 116,608 = 29,968,256 per
+    source, the pair (6,7) less.  The bound is 29,968,256 m: 1,917,968,384 at
+    m = 64, below 2^31 up to m = 71 and above it from m = 72 -- this kernel
+    is what limits the sources of one launch (LEAF_M)."""
+    tot = sum(_S)
+    return m * max(tot * (_E[b] + 256 * _E[b + 1]) for b in range(0, 8, 2))

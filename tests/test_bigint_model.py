@@ -220,6 +220,180 @@ def test_noise_bounds(pair):
     print(f'product noise 2^{got:.1f}, bound 2^{bound:.1f}')
 
 
+# --------------------------------------------- constants and their sums ---
+def test_scaled_const_definition():
+    """(k, sh) from the definition: exact rounding half away from zero up to
+    2^62 in magnitude, above it 62 leading bits and a shift"""
+    assert M.scaled_const(0.0) == (0, 0)
+    assert M.scaled_const(2.5) == (3, 0) and M.scaled_const(-2.5) == (-3, 0)
+    assert M.scaled_const(0.5) == (1, 0) and M.scaled_const(-0.5) == (-1, 0)
+    assert M.scaled_const(0.49999999999999994) == (0, 0)
+    assert M.scaled_const(2.0 ** 53 + 2) == (2 ** 53 + 2, 0)      # no floating-point + 0.5
+    assert M.scaled_const(2.0 ** 62) == (2 ** 62, 0) and M.scaled_const(-2.0 ** 62) == (-2 ** 62, 0)
+    assert M.scaled_const(2.0 ** 63) == (2 ** 62, 1)
+    assert M.scaled_const(-3.0 * 2.0 ** 100) == (-3 * 2 ** 60, 40)
+    rng = np.random.default_rng(10)
+    for x in np.ldexp(rng.uniform(-1, 1, 200), rng.integers(40, 140, 200)):
+        k, sh = M.scaled_const(x)
+        assert abs(k) <= 2 ** 62 and sh >= 0
+        assert abs(k * 2 ** sh - int(x)) <= 2 ** sh // 2 + 1, x
+        if sh:
+            assert abs(k) > 2 ** 60, x
+    q = (1 << 60) - 93
+    assert M.const_residue(-1, 0, q) == q - 1
+    assert M.const_residue(-2 ** 62, 7, q) == (-(2 ** 69)) % q
+
+
+def half_constant(scale):
+    """a double c with c * scale = k + 1/2 exactly (rounds away from zero)"""
+    for k in range(1, 4000):
+        c = (k + 0.5) / scale
+        if c * scale == k + 0.5:
+            return c, k
+    raise AssertionError('no constant lands on a half at this scale')
+
+
+PATTERNS = {
+    'zero': lambda q, n: np.zeros(n, dtype=np.uint64),
+    'q-1': lambda q, n: np.full(n, q - 1, dtype=np.uint64),
+    'alt 0/q-1': lambda q, n: np.where(np.arange(n) % 2 == 0, 0, q - 1).astype(np.uint64),
+    'q/2': lambda q, n: np.full(n, q // 2, dtype=np.uint64),
+    'q/2+1': lambda q, n: np.full(n, q // 2 + 1, dtype=np.uint64),
+    'ramp': lambda q, n: (np.arange(n, dtype=np.uint64) % np.uint64(q)),
+}
+
+
+def pattern_ct(name, primes, n):
+    w = np.stack([PATTERNS[name](int(q), n) for q in primes])
+    return np.stack([w, w[:, ::-1]])
+
+
+def large_constant(m):
+    """a constant whose product with a scale of this context exceeds 2^62"""
+    return 1.0e7 if m.q[1] < (1 << 42) else 37.5
+
+
+def test_constant_ops(pair):
+    """add_const, mul_const, mul_const_to, mul_int, level_adjust, linear_sum_to and
+    mul_plain_sum of the oracle against the model, on real encryptions and on
+    the edge patterns; constants 0, negative, on a half, and one in the
+    large-constant form (sh > 0, asserted from the model)"""
+    orc, m = pair
+    rng = np.random.default_rng(11)
+    delta = orc.delta
+    big = large_constant(m)
+    assert M.const_at_scale(big, delta[0])[1] > 0 and M.const_to_target(-big, delta[2], m.q[m.nq - 2], delta[1])[1] > 0
+    half, hk = half_constant(delta[1])
+    assert M.const_at_scale(half, delta[1]) == (hk + 1, 0) and M.const_at_scale(-half, delta[1]) == (-hk - 1, 0)
+    consts = [0.0, 1.0, -1.0, 0.37, -2.75, half, -half, big, -big]
+    for level in (0, 1):
+        ell = m.nq - level
+        cts = [('encryption', orc.encrypt(rng.uniform(-1, 1, 8), 8, level))]
+        cts += [(name, orc.ct_from(pattern_ct(name, m.q[:ell], m.n), level, 8)) for name in PATTERNS]
+        for name, oa in cts:
+            a, sc = oa.data(), oa.info()['scale']
+            tag = f'{name}, level {level}'
+            for c in consts:
+                assert np.array_equal(m.add_const(a, c, sc), orc.add_const(oa, c).data()), f'add_const {c}, {tag}'
+                assert np.array_equal(m.mul_const(a, c, sc, level, delta), orc.mul_const(oa, c).data()), \
+                    f'mul_const {c}, {tag}'
+            for c in (0.37, -big):
+                assert np.array_equal(m.mul_const_to(a, c, sc, level + 2, delta),
+                                      orc.mul_const_to(oa, c, level + 2).data()), f'mul_const_to {c}, {tag}'
+            for k in (0, 1, -1, 7, -3, 2 ** 62, -2 ** 62, 2 ** 40 + 1):
+                assert np.array_equal(m.mul_int(a, k), orc.mul_int(oa, k).data()), f'mul_int {k}, {tag}'
+            for t in (level, level + 1, level + 3):
+                assert np.array_equal(m.level_adjust(a, sc, level, t, delta), orc.level_adjust(oa, t).data()), \
+                    f'level_adjust to {t}, {tag}'
+        # sums over inputs of two limb counts, every pattern and the encryption together
+        lo = orc.encrypt(rng.uniform(-1, 1, 8), 8, 0)
+        xs = [oa for _, oa in cts] + ([lo] if level else [])
+        cs = [c for c, _ in zip(consts + [0.5, -0.25], xs)]
+        want = m.linear_sum_to([x.data() for x in xs], cs, [x.info()['scale'] for x in xs], level + 1, delta)
+        assert np.array_equal(want, orc.linear_sum_to(xs, cs, level + 1).data()), f'linear_sum_to, level {level}'
+        pts = [orc.encode(rng.uniform(-1, 1, 8), 8, level) for _ in xs[:len(cts)]]
+        want = m.mul_plain_sum([oa.data() for _, oa in cts], [p.data() for p in pts])
+        assert np.array_equal(want, orc.mul_plain_sum([oa for _, oa in cts], pts).data()), f'mul_plain_sum, level {level}'
+
+
+def test_linear_sums_is_the_sum_of_its_rows(pair):
+    """linear_sums (the GPU tests' reference for the multi-output kernels) row
+    by row against the oracle's linear_sum_to, and its constant fold against
+    add_const behind the rescale: the identity the fold relies on"""
+    orc, m = pair
+    rng = np.random.default_rng(12)
+    delta, target = orc.delta, 2
+    ell = m.nq - 1
+    xs = [orc.encrypt(rng.uniform(-1, 1, 8), 8, lv) for lv in (1, 1, 0)]
+    cs = [[0.5, -1.25, 3.0], [0.0, large_constant(m), -1.0]]
+    cc = [0.125, -0.7]
+    ks = [[M.const_to_target(c, delta[target], m.q[ell - 1], x.info()['scale']) for c, x in zip(row, xs)] for row in cs]
+    kc = [M.const_at_scale(c, delta[target]) for c in cc]
+    K, sh = [[k for k, _ in r] for r in ks], [[s for _, s in r] for r in ks]
+    assert any(s > 0 for r in sh for s in r)
+    plain = M.linear_sums([x.data() for x in xs], K, sh, m.q[:ell])
+    fold = M.linear_sums([x.data() for x in xs], K, sh, m.q[:ell], consts=([k for k, _ in kc], [s for _, s in kc]))
+    for g in range(2):
+        got = orc.linear_sum_to(xs, cs[g], target)
+        assert np.array_equal(m.rescale(plain[g]), got.data()), f'row {g}'
+        assert np.array_equal(fold[g][:, ell - 1], plain[g][:, ell - 1]), 'the fold touches the last limb'
+        assert np.array_equal(m.rescale(fold[g]), orc.add_const(got, cc[g]).data()), f'row {g} with its constant'
+
+
+# ------------------------------------------- the int32 budget of the rows ---
+def test_row_budget_bounds():
+    """the number that bounds the sources of one leaf-sum launch (LEAF_M = 64)"""
+    assert M.budget_bound_window(64) == 1682964480 < 2 ** 31
+    assert M.budget_bound_fold(64) == 1917968384 < 2 ** 31
+    assert M.budget_bound_window(72) < 2 ** 31 <= M.budget_bound_window(82) and M.budget_bound_window(81) < 2 ** 31
+    assert M.budget_bound_fold(71) < 2 ** 31 <= M.budget_bound_fold(72)
+    # a single row, which the MFMA accumulates in int32 as well
+    assert 64 * 911 * 128 < 2 ** 31
+
+
+ALL_MINUS_128_60 = 15 * 2 ** 56 - 0x80808080808080
+ALL_MINUS_128_40 = 2 ** 40 - 0x8080808080
+
+
+@pytest.mark.parametrize('q', [(1 << 60) - 93, (1 << 59) - 55, (1 << 40) + 294913, (1 << 41) - 21],
+                         ids=['60bit', '59bit', '40bit', '41bit'])
+def test_rows_recombine_to_the_exact_sum(q):
+    """the identity each kernel relies on, with its correction term (C0 sum c,
+    128 sum d), on random and on targeted words; every combined word inside the
+    proven bound; the targeted words reach further than random ones"""
+    rng = np.random.default_rng(q % 1000)
+    m, n = 17, 96
+    assert M.balanced_digits(ALL_MINUS_128_60) == [-128] * 7 + [15]
+    assert M.balanced_digits(ALL_MINUS_128_40) == [-128] * 5 + [1, 0, 0]
+    special = ALL_MINUS_128_60 if q > ALL_MINUS_128_60 else ALL_MINUS_128_40
+    assert special < q
+    res = [[int(v) for v in rng.integers(0, q, size=m)], [special] * m, [q - 1] * m, [0] + [1] * (m - 1)]
+    ys = rng.integers(0, q, size=(m, n), dtype=np.uint64)
+    ys[:, 0], ys[:, 1] = q - 1, 0
+    for form in ('window', 'fold'):
+        tw, triples = M.target_words(form, res, q, n)
+        assert int(tw.max()) < q
+        for g, r in enumerate(res):
+            reach = []
+            for words in (ys, tw):
+                exact = sum(M.obj(words[i]) * r[i] for i in range(m))
+                if form == 'window':
+                    rows, comb = M.rows_window(r, words)
+                    assert np.all(M.recombine_window(rows, r) == exact), (form, g)
+                    assert int(np.abs(comb).max()) <= M.budget_bound_window(m)
+                else:
+                    rows, comb = M.rows_fold(r, words, q)
+                    assert np.all((M.recombine_fold(rows, r, q) - exact) % q == 0), (form, g)
+                    assert int(np.abs(comb).max()) <= M.budget_bound_fold(m)
+                reach.append(int(np.abs(comb).max()))
+            if g == 0:
+                assert reach[1] > 2 * reach[0], (form, reach)
+    # zero words against the all -128 digits: a row of exactly 7 2^14 m (60-bit) in the window form
+    if q > (1 << 59):
+        rows, _ = M.rows_window([ALL_MINUS_128_60] * m, np.zeros((m, 1), dtype=np.uint64))
+        assert int(rows.max()) == 7 * 2 ** 14 * m
+
+
 @pytest.mark.parametrize('L,alpha,K', [(65, 22, 16), (61, 21, 15), (50, 17, 12)])
 def test_wide_digits_rotation(L, alpha, K):
     """the three wide-digit contexts of test_wide_digits_match_oracle at ring

@@ -25,7 +25,7 @@ def test_header_declares_the_boundary():
     for must in ('fhe_ctx_create', 'fhe_ctx_load_keys', 'fhe_ct_upload', 'fhe_ct_download', 'fhe_mul_relin',
                  'fhe_rotate', 'fhe_rotate_hoisted', 'fhe_cheb_ps', 'fhe_sign_composite', 'fhe_compare',
                  'fhe_indicator', 'fhe_direct_sort', 'fhe_comm_init', 'fhe_ct_allreduce', 'fhe_ntt', 'fhe_modup',
-                 'fhe_moddown', 'fhe_automorph'):
+                 'fhe_moddown', 'fhe_automorph', 'fhe_linear_sums_raw'):
         assert must in names
 
 
