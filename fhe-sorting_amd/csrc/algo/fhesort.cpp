@@ -2014,6 +2014,168 @@ std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext
     return outs;
 }
 
+GatherLevels gatherLevels(int pos_level, int N, int ps_split) {
+    if (pos_level < 0) throw std::invalid_argument("gather: negative position level");
+    std::vector<double> c(doubledSincCoefficients(N));
+    trim_zeros(c);
+    GatherLevels lv;
+    lv.diff_level = pos_level + 1;
+    // the 1/2N scaling, then the series: indexSeriesLevel of the differences' level
+    lv.series_level = lv.diff_level + 1 + chebPSDepthSplit((int)c.size() - 1, ps_split);
+    lv.col_max_level = lv.series_level - 2;
+    lv.out_level = lv.series_level + 1;
+    return lv;
+}
+
+// Gather by encrypted position.  groupSums' layout with the index check's
+// predicate: slot s of batch b holds pl[s mod N] - pr[(s mod N + t) mod N],
+// t = b P_ + s / N, and the equally shifted column beside it.  Per offset o the
+// difference becomes d = pl - pr + o, negated for o < 0 so that d > -N always (the
+// doubled series also fires at -N); the sort's series of d / 2N is 1 where the
+// right row stands o places after the left one, so series x column, summed over
+// batches and folded over the P_ partitions, is the neighbour's value.
+std::vector<CtPtr> DirectSortN::gatherColumns(const Ciphertext &pl, const Ciphertext &pr,
+                                              const std::vector<const Ciphertext *> &cols,
+                                              const std::vector<int> &offsets, bool want_present, bool sum_offsets) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)cols.size(), K = (int)offsets.size();
+    if (P == 0 && !want_present) throw std::invalid_argument("gather: neither a column nor the present flag is asked for");
+    if (K < 1) throw std::invalid_argument("gather: no offsets");
+    for (int k = 0; k < K; ++k)
+        if (offsets[k] < -(N - 1) || offsets[k] > N - 1)
+            throw std::invalid_argument("gather: offset " + std::to_string(k) + " (" + std::to_string(offsets[k]) +
+                                        ") is outside [-" + std::to_string(N - 1) + ", " + std::to_string(N - 1) + "]");
+    if (pl.batch != 1 || pr.batch != 1) throw std::invalid_argument("gather: a position is a stack");
+    if (pl.slots != pr.slots) throw std::invalid_argument("gather: the positions differ in slot count");
+    if (pl.level != pr.level)
+        throw std::invalid_argument("gather: the positions sit at different levels (" + std::to_string(pl.level) + ", " +
+                                    std::to_string(pr.level) + ")");
+    for (int p = 0; p < P; ++p) {
+        if (!cols[p]) throw std::invalid_argument("gather: column " + std::to_string(p) + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument("gather: column " + std::to_string(p) + " is a stack");
+        if (cols[p]->slots != pl.slots)
+            throw std::invalid_argument("gather: column " + std::to_string(p) + " has " + std::to_string(cols[p]->slots) +
+                                        " slots, the positions " + std::to_string(pl.slots));
+    }
+    const GatherLevels lv = gatherLevels(pl.level, N, cc.ps_split());
+    const int need = P > 0 ? lv.out_level : lv.series_level;
+    if (need > cc.params().L)
+        throw std::runtime_error("gather: positions at level " + std::to_string(pl.level) + " need " +
+                                 std::to_string(need) + " levels, the context has " + std::to_string(cc.params().L) +
+                                 ": no levels left");
+    for (int p = 0; p < P; ++p)
+        if (cols[p]->level > lv.col_max_level)
+            throw std::runtime_error("gather: column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
+                                     std::to_string(lv.col_max_level) + "): no levels left to meet the series");
+    if (!cache_masks) refresh_masks();
+    std::optional<AlgoPhase> ph;
+    ph.emplace("gather_baby");
+    std::vector<CtPtr> rbaby = babySteps(pr, s.np);
+    for (auto &b : rbaby) b->slots = s.num_slots;
+    // the columns, prepared once: brought to one level above the series output,
+    // then the baby steps every batch's shifted copy starts from
+    std::vector<std::vector<CtPtr>> cbaby(P);
+    for (int p = 0; p < P; ++p) {
+        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 1.0, lv.series_level - 1), s.np);
+        for (auto &b : cbaby[p]) b->slots = s.num_slots;
+    }
+    ph.reset();
+    std::vector<int> mine(s.num_batch);
+    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
+    CtPtr dup = cc.clone(pl);
+    dup->slots = s.num_slots;
+    cc.sync();  // the baby steps and dup are read by every lane
+    const int Ko = sum_offsets ? 1 : K;  // indicators that meet the columns, per batch
+    // batches per stacked series: max_stack members over the K offsets
+    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / K);
+    // columns per stacked product, as rotationIndexCheckColumns bounds them
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
+    const int per_product = std::max(1, std::max(1, max_col_members) / (Ko * (int)largest));
+    const std::vector<double> &coeffs = sincCoefficients();
+    std::vector<CtPtr> cnt_parts;  // every lane's present partial (level series_level)
+    std::mutex cnt_mu;
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph("gather_batches");
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        CtPtr cnt;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr r;
+            {
+                std::vector<CtPtr> shifted = vecRotsOptMany(L, rbaby, s.num_partition, s.num_slots, s.np, iss);
+                std::vector<const Ciphertext *> ptrs;
+                for (auto &x : shifted) ptrs.push_back(x.get());
+                CtPtr d = E.sub_offsets_stacked(*dup, ptrs, offsets);  // member k B + z
+                shifted.clear();
+                r = evalChebyshevSeriesPS(E, *E.mul_const(*d, 1.0 / N / 2), coeffs, -1.0, 1.0);
+            }
+            if (r->level != lv.series_level) throw std::logic_error("gather: unexpected series output level");
+            if (sum_offsets && K > 1) {  // the frame: the offsets' indicators added, exact mod q
+                const size_t words = (size_t)B * 2 * r->limbs * E.n();
+                Ciphertext v = *r;
+                v.batch = B;
+                CtPtr sum = E.clone(v);
+                for (int k = 1; k < K; ++k) {
+                    v.data = r->data + (size_t)k * words;
+                    E.add_inplace(sum, v);
+                }
+                r = sum;
+            }
+            if (want_present) E.sum_member_groups(*r, Ko, cnt);
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
+                for (int p = p0; p < p0 + Pg; ++p)
+                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
+                CtPtr prod = E.mul_gather(*r, *asStack(E, sv), Pg, Ko);  // member ((p - p0) Ko + k) B + z
+                sv.clear();
+                E.sum_member_groups(*prod, Pg * Ko, accs[g]);
+            }
+        }
+        if (cnt) {
+            std::lock_guard<std::mutex> lk(cnt_mu);
+            cnt_parts.push_back(cnt);
+        }
+        if (bs.empty() || P == 0) return nullptr;
+        if (accs.size() == 1) return accs[0];
+        std::vector<const Ciphertext *> all;
+        for (auto &a : accs) all.push_back(a.get());
+        return E.stack(all);  // the column groups, in column order
+    });
+    CtPtr out, cnt;
+    for (auto &p : parts)
+        if (p) cc.add_inplace(out, *p);
+    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    cnt_parts.clear();
+    AlgoPhase fold_ph("gather_fold");
+    auto fold = [&](CtPtr &v) {
+        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    };
+    std::vector<CtPtr> outs;
+    if (P > 0) {
+        fold(out);
+        for (int m = 0; m < P * Ko; ++m) {
+            outs.push_back(P * Ko == 1 ? out : cc.clone(*cc.member(*out, m)));
+            outs.back()->slots = N;
+        }
+    }
+    if (want_present) {
+        fold(cnt);
+        for (int k = 0; k < Ko; ++k) {
+            outs.push_back(Ko == 1 ? cnt : cc.clone(*cc.member(*cnt, k)));
+            outs.back()->slots = N;
+        }
+    }
+    return outs;
+}
+
 // Running sums.  groupSums' layout with the rank's own predicate: slot s of batch b
 // holds kl[s mod N] - kr[(s mod N + t) mod N] (+ the mode's offset), t = b P_ + s / N,
 // and the equally shifted column beside it.  The indicator is s + 1 (2 or 0) for

@@ -224,6 +224,19 @@ struct WindowSumLevels {
 };
 WindowSumLevels windowSumLevels(int key_level, int nfactors, int n, int dg, int df, int ps_split = PS_SPLIT_OPENFHE);
 
+// Levels of DirectSortN::gatherColumns for positions at pos_level over N rows: the
+// differences at diff_level = pos_level + 1 (one masked sum below the positions),
+// the series output (and the present flags) at series_level = diff_level + 1 +
+// the doubled-sinc series' depth under `ps_split` (DirectSortN::indexSeriesLevel of
+// diff_level), the columns brought to series_level - 1 before their own masked
+// sum, so a column may sit at col_max_level = series_level - 2 at most, and every
+// gathered column at out_level = series_level + 1.  Throws std::invalid_argument on
+// a negative level, std::runtime_error where N has no coefficient table.
+struct GatherLevels {
+    int diff_level, series_level, col_max_level, out_level;
+};
+GatherLevels gatherLevels(int pos_level, int N, int ps_split = PS_SPLIT_OPENFHE);
+
 // Sums a ciphertext's u64 limbs over ranks in place (device pointer, count
 // u64); the engine reduces mod q afterwards.  nullptr = single rank.
 using CtAllReduce = std::function<void(u64 *dev_data, size_t count)>;
@@ -389,6 +402,31 @@ class DirectSortN {
                                   const Ciphertext *ol, const Ciphertext *olo, const Ciphertext *orr,
                                   const std::vector<const Ciphertext *> &cols, int mode, double eps, bool want_count,
                                   SignFunc f, const SignConfig &cfg);
+    // Gather by encrypted position (the project's own extension):
+    // with P = cols.size() and K = offsets.size(), the output for column p and
+    // offset o holds at slot e  sum_j delta(pl_e + o - pr_j) cols[p]_j, j over the N
+    // right rows: the value of the right row standing o places after left row e's
+    // position, zero where there is none.  pl = pr = a rank gives LAG / LEAD; an
+    // encrypted iota as pr and encrypted indices as pl give the lookup col[idx].
+    // pl and pr hold integers in [0, N) up to the noise a rank carries, the pr
+    // distinct; |o| <= N - 1.  constructRank's all-pairs layout with the shifted
+    // right positions and the same shifted copies of the columns; the oriented
+    // differences of a chunk of B batches and the K offsets are one K B stack
+    // (Engine::sub_offsets_stacked: pl - pr + o, negated for o < 0 so that it stays
+    // above -N, where the doubled series fires too), the sort's 1/2N scaling and
+    // doubled-sinc series run once over it, and it meets the columns in one
+    // stacked product (Engine::mul_gather); sums over batches are exact mod q,
+    // then the rank's fold.  want_present appends the same sums without the
+    // column (1 where the neighbour exists), at the series' level.  sum_offsets
+    // adds the K indicators of a batch before the product: one output per column,
+    // the sum over the offsets (ROWS BETWEEN), and present the frame's row count.
+    // Outputs: column-major (p K + k), then the present flags.  Levels:
+    // gatherLevels; a column above col_max_level or a context without the levels
+    // is refused before any work.  The words do not depend on max_stack, lanes,
+    // max_col_members or cache_masks.  Unsharded; `tiebreak` has no effect.
+    std::vector<CtPtr> gatherColumns(const Ciphertext &pl, const Ciphertext &pr,
+                                     const std::vector<const Ciphertext *> &cols, const std::vector<int> &offsets,
+                                     bool want_present, bool sum_offsets);
     // level of the index check's series output for a rank at rank_level: where
     // the product meets the column
     int indexSeriesLevel(int rank_level) const;

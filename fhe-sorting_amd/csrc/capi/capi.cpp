@@ -784,6 +784,101 @@ int fhe_group_sum_levels(int key_level, int n, int dg, int df, int *col_max_leve
         if (out_level) *out_level = lv.out_level;
     });
 }
+int fhe_direct_gather(fhe_ctx *ctx, const fhe_ct *pos_l, const fhe_ct *pos_r, const fhe_ct *const *cols, int ncols,
+                      const int32_t *offsets, int noffsets, int want_present, int sum_offsets, int N,
+                      const int32_t *rots, int nrot, fhe_ct **outs) {
+    const int ko = sum_offsets ? 1 : std::max(noffsets, 0);
+    const long long nout = ((long long)std::max(ncols, 0) + (want_present ? 1 : 0)) * ko;
+    if (outs)
+        for (long long i = 0; i < nout; ++i) outs[i] = nullptr;
+    return guard([&] {
+        NEED(ctx);
+        if (!pos_l || !pos_l->p) throw std::invalid_argument("fhe_direct_gather: the left position is null");
+        if (!pos_r || !pos_r->p) throw std::invalid_argument("fhe_direct_gather: the right position is null");
+        if (ncols < 0) throw std::invalid_argument("fhe_direct_gather: ncols must be >= 0");
+        if (noffsets < 1 || !offsets) throw std::invalid_argument("fhe_direct_gather: noffsets must be >= 1");
+        if (ncols == 0 && !want_present)
+            throw std::invalid_argument("fhe_direct_gather: neither a column nor the present flag is asked for");
+        if (!outs || (ncols > 0 && !cols)) throw std::invalid_argument("fhe_direct_gather: null column or output array");
+        for (int k = 0; k < noffsets; ++k)
+            if (offsets[k] < -(N - 1) || offsets[k] > N - 1)
+                throw std::invalid_argument("fhe_direct_gather: offset " + std::to_string(k) + " (" +
+                                            std::to_string(offsets[k]) + ") is outside [-(N - 1), N - 1]");
+        const Ciphertext &pl = *pos_l->p, &pr = *pos_r->p;
+        if (pl.batch != 1) throw std::invalid_argument("fhe_direct_gather: the left position is a stack");
+        if (pr.batch != 1) throw std::invalid_argument("fhe_direct_gather: the right position is a stack");
+        if (pr.slots != pl.slots)
+            throw std::invalid_argument("fhe_direct_gather: the right position has " + std::to_string(pr.slots) +
+                                        " slots, the left position " + std::to_string(pl.slots));
+        if (pr.level != pl.level)
+            throw std::invalid_argument("fhe_direct_gather: the positions sit at different levels (" +
+                                        std::to_string(pl.level) + ", " + std::to_string(pr.level) + ")");
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < ncols; ++p) {
+            const std::string which = "fhe_direct_gather: column " + std::to_string(p);
+            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
+            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
+            if (cols[p]->p->slots != pl.slots)
+                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) +
+                                            " slots, the positions " + std::to_string(pl.slots));
+            v.push_back(cols[p]->p.get());
+        }
+        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+        auto &slot = ctx->sorters[skey];
+        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
+        DirectSortN &ds = *slot;
+        ds.max_stack = ctx->sort_stack;
+        ds.lanes = ctx->sort_lanes;
+        ds.max_col_members = ctx->sort_col_members;
+        ds.cache_masks = ctx->mask_cache;
+        ds.shard_rank = 0;  // unsharded, like the select
+        ds.shard_world = 1;
+        ds.allreduce = nullptr;
+        // the depth refusals (a column too deep, a context too shallow) are raised
+        // by the operator before it starts any work
+        std::vector<CtPtr> r = ds.gatherColumns(pl, pr, v, std::vector<int>(offsets, offsets + noffsets),
+                                                want_present != 0, sum_offsets != 0);
+        if ((long long)r.size() != nout) throw std::logic_error("fhe_direct_gather: unexpected output count");
+        for (size_t i = 0; i < r.size(); ++i) outs[i] = wrap(r[i]);
+    });
+}
+int fhe_gather_levels(int pos_level, int N, int *col_max_level, int *series_level, int *out_level) {
+    return guard([&] {
+        if (N < 1) throw std::invalid_argument("fhe_gather_levels: N must be >= 1");
+        const GatherLevels lv = gatherLevels(pos_level, N);
+        if (col_max_level) *col_max_level = lv.col_max_level;
+        if (series_level) *series_level = lv.series_level;
+        if (out_level) *out_level = lv.out_level;
+    });
+}
+int fhe_sub_offsets_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, int count, const int32_t *offsets,
+                            int noffsets, fhe_ct **out) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a);
+        NEED(bs);
+        NEED(offsets);
+        NEED(out);
+        if (count < 1) throw std::invalid_argument("fhe_sub_offsets_stacked: count must be >= 1");
+        if (noffsets < 1) throw std::invalid_argument("fhe_sub_offsets_stacked: noffsets must be >= 1");
+        std::vector<const Ciphertext *> b;
+        for (int i = 0; i < count; ++i) {
+            NEED(bs[i]);
+            b.push_back(bs[i]->p.get());
+        }
+        *out = wrap(ctx->eng->sub_offsets_stacked(*a->p, b, std::vector<int>(offsets, offsets + noffsets)));
+    });
+}
+int fhe_mul_gather(fhe_ctx *ctx, const fhe_ct *a_stack, const fhe_ct *b_stack, int ncols, int noffsets,
+                   fhe_ct **out_stack) {
+    return guard([&] {
+        NEED(ctx);
+        NEED(a_stack);
+        NEED(b_stack);
+        NEED(out_stack);
+        *out_stack = wrap(ctx->eng->mul_gather(*a_stack->p, *b_stack->p, ncols, noffsets));
+    });
+}
 int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, int count, double c,
                              fhe_ct **out) {
     return guard([&] {

@@ -1523,6 +1523,117 @@ __global__ __launch_bounds__(NT) void k_tensor_pairs(u64 *d01, u64 *d2, const u6
     }
 }
 
+// The oriented, offset differences of a chunk of comparator batches (gatherColumns,
+// DESIGN.md §6.8): with d_z = a - b_z and K public offsets, member k * stride + z
+// of out = d_z with w_k added to c0 for an offset >= 0 and the negation of that
+// (both halves) for an offset < 0, the whole K B stack written in one pass from
+// one load of b_z; a's two pairs of words are loaded once per tile of SOF_TM
+// batches: 2 K B + 2 B + 2 ceil(B / TM) limb-units against the (6 + 4 K + 4 K-) B
+// of sub_stacked, an add_const per offset and a negate per negative one (K- of
+// them).  sub_mod, add_mod of the constant's residue, sub_mod(0, .): the words
+// of k_sub, k_c0_op (mode 0) and k_neg.  A last tile narrower than SOF_TM repeats
+// its last batch and stores only the valid ones.
+// grid: x = coefficient block, y = limb, z = batch tile.
+constexpr int SOF_TM = 4;
+constexpr int SOF_KMAX = 32;
+struct SubOffsetsArgs {
+    const u64 *b[LIN_MAX];
+    int64_t K[SOF_KMAX];
+    uint8_t sh[SOF_KMAX];
+    uint8_t neg[SOF_KMAX];
+    int B, nk;
+};
+__global__ __launch_bounds__(NT) void k_sub_offsets_stacked(u64 *out, const u64 *a, SubOffsetsArgs A, size_t stride,
+                                                            size_t ln_all, const Mod *mods, int logN) {
+    constexpr int TM = SOF_TM;
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const u64 q = mods[l].q;
+    const size_t lo = (size_t)l * n + k;
+    const int m0 = blockIdx.z * TM;
+    const ulonglong2 a0 = ld2(a + lo), a1 = ld2(a + ln_all + lo);
+    ulonglong2 d0[TM], d1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        const int m = min(m0 + t, A.B - 1);  // block-uniform
+        d0[t] = ld2(A.b[m] + lo);
+        d1[t] = ld2(A.b[m] + ln_all + lo);
+    }
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+        d0[t] = make_ulonglong2(sub_mod(a0.x, d0[t].x, q), sub_mod(a0.y, d0[t].y, q));
+        d1[t] = make_ulonglong2(sub_mod(a1.x, d1[t].x, q), sub_mod(a1.y, d1[t].y, q));
+    }
+    for (int j = 0; j < A.nk; ++j) {
+        const u64 w = smod(A.K[j], A.sh[j], mods[l]);
+        const bool neg = A.neg[j] != 0;  // block-uniform
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < A.B) {
+                ulonglong2 v0 = make_ulonglong2(add_mod(d0[t].x, w, q), add_mod(d0[t].y, w, q)), v1 = d1[t];
+                if (neg) {
+                    v0 = make_ulonglong2(sub_mod(0, v0.x, q), sub_mod(0, v0.y, q));
+                    v1 = make_ulonglong2(sub_mod(0, v1.x, q), sub_mod(0, v1.y, q));
+                }
+                u64 *o = out + ((size_t)j * stride + (size_t)(m0 + t)) * 2 * ln_all + lo;
+                st2(o, v0);
+                st2(o + ln_all, v1);
+            }
+    }
+}
+
+// k_tensor of the series stack a (K * members members, member k * members + z)
+// against the column-major stack b of P * members shifted columns (gatherColumns'
+// indicators against the shifted columns): grid z = (p * ceil(K / KC)
+// + tile) * members + z; a thread loads column (p, z)'s two pairs of words once and
+// forms the tensor of the up to KC series members of its tile against them, every
+// member's loads issued ahead of the arithmetic.  Output member (p * K + k) * members
+// + z, the words k_tensor gives on (a[k * members + z], b[p * members + z]).  The
+// last tile is guarded.
+template <int KC>
+__global__ __launch_bounds__(NT) void k_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
+                                                      int P, int K, int members, const Mod *mods, int logN) {
+    const size_t n = (size_t)1 << logN;
+    const int l = blockIdx.y;
+    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
+    if (k >= n) return;
+    const Mod m = mods[l];
+    const unsigned tiles = (unsigned)(K + KC - 1) / KC;
+    const int z = (int)(blockIdx.z % (unsigned)members);
+    const unsigned g = blockIdx.z / (unsigned)members;
+    const int k0 = (int)(g % tiles) * KC, p = (int)(g / tiles);
+    const size_t o = (size_t)l * n + k;
+    const u64 *Bp = b + ((size_t)p * members + z) * 2 * ln_all;
+    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
+    ulonglong2 a0[KC], a1[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+        if (k0 + j < K) {
+            const u64 *Ap = a + ((size_t)(k0 + j) * members + z) * 2 * ln_all;
+            a0[j] = ld2(Ap + o);
+            a1[j] = ld2(Ap + ln_all + o);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+        if (k0 + j < K) {
+            ulonglong2 e0, e1, e2;
+            e0.x = mul_barrett(a0[j].x, b0.x, m);
+            e0.y = mul_barrett(a0[j].y, b0.y, m);
+            e1.x = add_mod(mul_barrett(a0[j].x, b1.x, m), mul_barrett(a1[j].x, b0.x, m), m.q);
+            e1.y = add_mod(mul_barrett(a0[j].y, b1.y, m), mul_barrett(a1[j].y, b0.y, m), m.q);
+            e2.x = mul_barrett(a1[j].x, b1.x, m);
+            e2.y = mul_barrett(a1[j].y, b1.y, m);
+            const size_t mo = ((size_t)p * K + (k0 + j)) * members + z;
+            st2(d01 + mo * 2 * ln_all + o, e0);
+            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
+            st2(d2 + mo * ln_all + o, e2);
+        }
+    }
+}
+
 // The differences of a chunk of comparator batches under L lexicographic keys
 // (lexRank), all written straight into one stack of
 // (2 L - 1) `count` members.  With d = a_key - b_{key, i}: a leading key writes
@@ -3743,6 +3854,48 @@ void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *
         launch_clocked(inst_name<TC_PC>("k_tensor_pairs"), B, k_tensor_pairs<TC_PC>, ew_grid(logN, limbs, members * groups),
                        dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, a2, b + mo * 2 * ln_all, ln_all, sa, Pn,
                        members, mods, logN);
+    }
+}
+int sub_offsets_tile() { return SOF_TM; }
+void ew_sub_offsets_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, const int64_t *Ks,
+                            const int *shs, const uint8_t *negs, int noff, int limbs, const Mod *mods, int logN,
+                            hipStream_t st) {
+    if (limbs <= 0 || members <= 0 || noff <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    for (int kb = 0; kb < noff; kb += SOF_KMAX)
+        for (int base = 0; base < members; base += LIN_MAX) {
+            SubOffsetsArgs A{};
+            A.B = std::min(LIN_MAX, members - base);
+            A.nk = std::min(SOF_KMAX, noff - kb);
+            for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
+            for (int j = 0; j < A.nk; ++j) {
+                A.K[j] = Ks[kb + j];
+                A.sh[j] = (uint8_t)shs[kb + j];
+                A.neg[j] = negs[kb + j];
+            }
+            const int tiles = (A.B + SOF_TM - 1) / SOF_TM;
+            const double B = 8.0 * (2.0 * A.nk * A.B + 2.0 * A.B + 2.0 * tiles) * ln_all;
+            launch_clocked("k_sub_offsets_stacked", B, k_sub_offsets_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
+                           out + ((size_t)kb * members + base) * 2 * ln_all, a, A, (size_t)members, ln_all, mods, logN);
+        }
+}
+constexpr int TG_KC = 4;
+int tensor_gather_per_thread() { return TG_KC; }
+void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int K, int limbs, int members,
+                      const Mod *mods, int logN, hipStream_t st) {
+    if (limbs <= 0 || members <= 0 || P <= 0 || K <= 0) return;
+    const size_t ln_all = (size_t)limbs << logN;
+    const int tiles = (K + TG_KC - 1) / TG_KC;
+    if ((long long)members * tiles > 65535) throw std::invalid_argument("ew_tensor_gather: too many members per column");
+    // grid z = members * tiles * columns stays below the 65535 limit: whole columns per launch
+    const int per_launch = std::max(1, 65535 / (members * tiles));
+    for (int base = 0; base < P; base += per_launch) {
+        const int Pn = std::min(per_launch, P - base);
+        const double B = 8.0 * (2.0 * members * tiles * Pn + 5.0 * Pn * K * members) * ln_all;
+        const size_t mo = (size_t)base * K * members;  // first output member of this launch
+        launch_clocked(inst_name<TG_KC>("k_tensor_gather"), B, k_tensor_gather<TG_KC>,
+                       ew_grid(logN, limbs, members * tiles * Pn), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a,
+                       b + (size_t)base * members * 2 * ln_all, ln_all, Pn, K, members, mods, logN);
     }
 }
 int sub_lex_tile() { return SLX_TM; }

@@ -288,6 +288,23 @@ void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int m
 int tensor_pairs_per_thread();
 void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
                      size_t sa, const Mod *mods, int logN, hipStream_t st);
+// With d_z = a - bs[z] (a, bs[z]: [2][limbs][n]): member k * members + z of out
+// ([noff members][2][limbs][n]) = d_z with Ks[k] 2^shs[k] added to c0, negated
+// (both halves) where negs[k] is set, in one pass.  A thread loads each bs[z]
+// once for all offsets and applies a's words to up to sub_offsets_tile() batches;
+// word for word ew_sub, then ew_c0_op mode 0, then ew_neg, per member.
+int sub_offsets_tile();
+void ew_sub_offsets_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, const int64_t *Ks,
+                            const int *shs, const uint8_t *negs, int noff, int limbs, const Mod *mods, int logN,
+                            hipStream_t st);
+// ew_tensor of the stack a (K * members members, member k * members + z) against
+// the column-major stack b of P * members members ([2][limbs][n] each) in one
+// pass: member (p * K + k) * members + z of d01 / d2 holds the tensor of
+// (a[k * members + z], b[p * members + z]), word for word ew_tensor's.  A column's
+// words are loaded once per tensor_gather_per_thread() members of a.
+int tensor_gather_per_thread();
+void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int K, int limbs, int members,
+                      const Mod *mods, int logN, hipStream_t st);
 // The stacked differences of `keys` lexicographic keys (as[key]: [2][limbs][n];
 // bs key-major, bs[key * count + i]; ps: `count` plaintexts [limbs][n] or nullptr)
 // in one pass: with d = as[key] - bs[key * count + i], member (2 key) count + i of

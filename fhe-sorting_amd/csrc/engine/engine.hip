@@ -2667,6 +2667,118 @@ CtPtr Engine::sub_pm_const_stacked(const Ciphertext &a0, const std::vector<const
     count_bytes(6.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
+// FHE_GATHER_FUSED (A/B, default 1): the one-pass kernels of sub_offsets_stacked and mul_gather
+static bool gather_fused_enabled() {
+    static const int on = [] {
+        const char *e = std::getenv("FHE_GATHER_FUSED");
+        return e ? std::atoi(e) : 1;
+    }();
+    return on != 0;
+}
+CtPtr Engine::sub_offsets_stacked(const Ciphertext &a0, const std::vector<const Ciphertext *> &bs,
+                                  const std::vector<int> &offsets) {
+    if (bs.empty()) throw std::invalid_argument("sub_offsets_stacked: no operands");
+    if (offsets.empty()) throw std::invalid_argument("sub_offsets_stacked: no offsets");
+    if (a0.batch != 1) throw std::invalid_argument("sub_offsets_stacked: a must be one ciphertext");
+    for (auto *b : bs)
+        if (!b || b->level != bs[0]->level || b->batch != 1)
+            throw std::invalid_argument("sub_offsets_stacked: operands differ in level");
+    const int B = (int)bs.size(), K = (int)offsets.size();
+    auto oriented = [&](const Ciphertext &d, int o) {  // d + o, negated for o < 0
+        CtPtr v = add_const(d, (double)o);
+        return o < 0 ? negate(*v) : v;
+    };
+    if (a0.level > bs[0]->level) {  // every b is adjusted instead: per-member ops, as sub_stacked
+        std::vector<CtPtr> d((size_t)K * B);
+        std::vector<const Ciphertext *> v;
+        for (int i = 0; i < B; ++i) {
+            CtPtr di = sub(a0, *bs[i]);
+            for (int k = 0; k < K; ++k) d[(size_t)k * B + i] = oriented(*di, offsets[k]);
+        }
+        for (auto &x : d) v.push_back(x.get());
+        return stack(v);
+    }
+    if (!gather_fused_enabled()) {  // the plain form (A/B): the stacked differences, then every offset on the stack
+        CtPtr d = sub_stacked(a0, bs);
+        if (K == 1) return oriented(*d, offsets[0]);
+        std::vector<CtPtr> parts;
+        std::vector<const Ciphertext *> v;
+        for (int k = 0; k < K; ++k) {
+            parts.push_back(oriented(*d, offsets[k]));
+            v.push_back(parts.back().get());
+        }
+        return stack(v);
+    }
+    CtPtr a = std::make_shared<Ciphertext>(a0);
+    if (a->level < bs[0]->level) a = level_adjust(*a, bs[0]->level);  // sub(a, b) adjusts a the same way
+    const size_t ell = a->limbs;
+    auto r = new_ct(a->level, a->slots, a->scale, ell, K * B);
+    std::vector<const u64 *> bp;
+    for (auto *b : bs) {
+        if (b->limbs != ell)  // the kernel reads ell limbs of each
+            throw std::invalid_argument("sub_offsets_stacked: operand limb count differs from its level's");
+        bp.push_back(b->data);
+    }
+    std::vector<int64_t> Ks(K);
+    std::vector<int> shs(K);
+    std::vector<uint8_t> negs(K);
+    for (int k = 0; k < K; ++k) {
+        const host::SConst C = host::const_at_scale((double)offsets[k], a->scale);
+        Ks[k] = C.k;
+        shs[k] = C.sh;
+        negs[k] = offsets[k] < 0;
+    }
+    dev::ew_sub_offsets_stacked(r->data, a->data, bp.data(), B, Ks.data(), shs.data(), negs.data(), K, (int)ell, MODS,
+                                LOGN, ST);
+    const int tile = dev::sub_offsets_tile();
+    count_bytes((2.0 * K + 2.0) * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
+    return r;
+}
+CtPtr Engine::mul_gather(const Ciphertext &a, const Ciphertext &b, int Pn, int Kn) {
+    auto &I = *impl;
+    if (Pn < 1) throw std::invalid_argument("mul_gather: no columns");
+    if (Kn < 1) throw std::invalid_argument("mul_gather: no offsets");
+    if (a.batch < 1 || a.batch % Kn != 0)
+        throw std::invalid_argument("mul_gather: a holds " + std::to_string(a.batch) + " members, not a multiple of " +
+                                    std::to_string(Kn) + " offsets");
+    const int B = a.batch / Kn;
+    if ((long long)b.batch != (long long)Pn * B)
+        throw std::invalid_argument("mul_gather: b holds " + std::to_string(b.batch) + " members, need " +
+                                    std::to_string(Pn) + " columns of " + std::to_string(B));
+    if (b.level != a.level || b.limbs != a.limbs) throw std::invalid_argument("mul_gather: b is not at a's level");
+    const int PKB = Pn * Kn * B;
+    const size_t nn = n(), ell = a.limbs;
+    if (!gather_fused_enabled()) {  // the plain form (A/B): one stacked mul per (column, offset), stacked
+        std::vector<CtPtr> prod;
+        std::vector<const Ciphertext *> v;
+        for (int p = 0; p < Pn; ++p)
+            for (int k = 0; k < Kn; ++k) {
+                Ciphertext col = b, ser = a;
+                col.data = b.data + (size_t)p * B * 2 * ell * nn;
+                ser.data = a.data + (size_t)k * B * 2 * ell * nn;
+                col.batch = ser.batch = B;
+                prod.push_back(mul(ser, col));
+                v.push_back(prod.back().get());
+            }
+        return prod.size() == 1 ? prod[0] : stack(v);
+    }
+    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    ctr.hmult += PKB;
+    ctr.keyswitch += PKB;
+    ctr.rescale += PKB;
+    count_bytes(5.0 * ell + ks_units(ell), PKB);
+    const int per = dev::tensor_gather_per_thread();
+    count_bytes(2.0 * ell * ((Kn + per - 1) / per), Pn * B);
+    auto d01m = I.alloc((size_t)PKB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PKB * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    dev::ew_tensor_gather(d01, d2, a.data, b.data, Pn, Kn, (int)ell, B, MODS, LOGN, ST);
+    const bool fuse = I.ks_fuse(PKB);
+    auto extm = I.modup(d2, ell, PKB, ell * nn, fuse);
+    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PKB);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PKB, r->data, fuse);
+    return r;
+}
 // FHE_LEX_FUSED (A/B, default 1): the one-pass kernels of sub_lex_stacked and mul_lex
 static bool lex_fused_enabled() {
     static const int on = [] {

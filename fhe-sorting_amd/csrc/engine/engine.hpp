@@ -343,6 +343,23 @@ class Engine {
     // rules.  FHE_GROUP_FUSED=0 (A/B): sub_stacked, then negate / add_const on
     // the stack, stacked.
     CtPtr sub_pm_const_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs, double c);
+    // The oriented, offset differences of the gather (DirectSortN::gatherColumns,
+    // DESIGN.md §6.8): with B = bs.size() and K = offsets.size(), member k B + i =
+    // add_const(sub(a, bs[i]), offsets[k]) for an offset >= 0 and the negate of that
+    // for an offset < 0, word for word, written straight into the K B stack by one
+    // launch (k_sub_offsets_stacked: each bs[i] loaded once for all offsets, a's
+    // words once per tile of members).  sub_stacked's level rules.
+    // FHE_GATHER_FUSED=0 (A/B): sub_stacked, then add_const / negate on the stack
+    // per offset, stacked.
+    CtPtr sub_offsets_stacked(const Ciphertext &a, const std::vector<const Ciphertext *> &bs,
+                              const std::vector<int> &offsets);
+    // the K B-member stack a (member k B + z) against the column-major stack b of
+    // P B members, all at one level: member (p K + k) B + z of the result is
+    // mul(member(a, k B + z), member(b, p B + z)) word for word.  One tensor pass
+    // (k_tensor_gather: a column's words loaded once per thread for up to four
+    // offsets), then mul's relinearisation / rescale tail on P K B members.
+    // FHE_GATHER_FUSED=0 (A/B): one stacked mul per (column, offset), stacked.
+    CtPtr mul_gather(const Ciphertext &a, const Ciphertext &b, int P, int K);
     // The differences of lexicographic keys (DirectSortN::lexRank):
     // with L = as.size() keys (2..4), count = bs.size() / L and bs key-major
     // (bs[l count + i]), the result is a stack of (2 L - 1) count members: for a

@@ -152,6 +152,12 @@ _SIGS = {
     'fhe_sub_pm_const_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_double,
                                            C.POINTER(C.c_void_p)]),
     'fhe_mul_pairs': (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_direct_gather': (C.c_int, [vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    ip, C.c_int, C.POINTER(C.c_void_p)]),
+    'fhe_gather_levels': (C.c_int, [C.c_int, C.c_int, ip, ip, ip]),
+    'fhe_sub_offsets_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, ip, C.c_int,
+                                          C.POINTER(C.c_void_p)]),
+    'fhe_mul_gather': (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_direct_running_sum': (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_int,
                                          ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p)]),
@@ -927,6 +933,56 @@ class Context:
         mul(add(member(a, z), member(a_add, z)), member(b_stack, p * B + z)) word for word"""
         return self._new(lib().fhe_mul_pairs, a.h, a_add.h, b_stack.h, ncols)
 
+    def gather(self, pos_l, pos_r, cols, offsets, N, rots, present=False, sum_offsets=False):
+        """Gather by encrypted position (fhe_direct_gather): for column p and offset k
+        the output has N slots, slot e holds cols[p] at the right row j whose position
+        pos_r[j] equals pos_l[e] + offsets[k], zero where there is none.  The positions
+        hold integers in [0, N) up to a rank's noise, the right ones distinct; |offset|
+        <= N - 1.  Returns the gathered columns column-major (index p * K + k);
+        present=True returns (outs, flags), flags[k] holding 1 where the neighbour
+        exists.  sum_offsets=True adds the offsets' indicators before the product: one
+        output per column, the sum over the offsets (ROWS BETWEEN), and one flag, the
+        frame's row count.  A column may sit at gather_levels(...)[0] at most."""
+        r = np.asarray(rots, dtype=np.int32)
+        off = np.asarray(list(offsets), dtype=np.int32)
+        cols = list(cols)
+        ko = 1 if sum_offsets else len(off)
+        nout = (len(cols) + (1 if present else 0)) * ko
+        arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
+        outs = (C.c_void_p * max(1, nout))()
+        _chk(lib().fhe_direct_gather(self.h, None if pos_l is None else pos_l.h, None if pos_r is None else pos_r.h,
+                                     arr, len(cols), _int(off), len(off), int(bool(present)), int(bool(sum_offsets)),
+                                     N, _int(r), len(r), outs))
+        res = [Ct(self, outs[i]) for i in range(nout)]
+        return (res[:len(cols) * ko], res[len(cols) * ko:]) if present else res
+
+    def lag(self, rank, cols, k, N, rots, present=False):
+        """LAG(v, k) in rank order: gather with pos_l = pos_r = rank and offset -k"""
+        return self.gather(rank, rank, cols, [-int(k)], N, rots, present=present)
+
+    def lead(self, rank, cols, k, N, rots, present=False):
+        """LEAD(v, k) in rank order: gather with pos_l = pos_r = rank and offset +k"""
+        return self.gather(rank, rank, cols, [int(k)], N, rots, present=present)
+
+    @staticmethod
+    def gather_levels(pos_level, N):
+        return gather_levels(pos_level, N)
+
+    def sub_offsets_stacked(self, a, bs, offsets):
+        """stack of len(offsets) * len(bs) members: member k * len(bs) + i is
+        add_const(sub(a, bs[i]), offsets[k]), negated for offsets[k] < 0, word for word,
+        in one pass"""
+        ba = (C.c_void_p * max(1, len(bs)))(*[b.h for b in bs])
+        off = np.asarray(list(offsets), dtype=np.int32)
+        return self._new(lib().fhe_sub_offsets_stacked, a.h, ba, len(bs), _int(off), len(off))
+
+    def mul_gather(self, a_stack, b_stack, ncols, noffsets):
+        """the noffsets * B-member stack a_stack (member k * B + z) against the
+        column-major stack b_stack of ncols * B members: member (p * noffsets + k) * B + z
+        of the result is mul(member(a_stack, k * B + z), member(b_stack, p * B + z)) word
+        for word"""
+        return self._new(lib().fhe_mul_gather, a_stack.h, b_stack.h, ncols, noffsets)
+
     def running_sum(self, left_key, right_key, cols, eps, N, rots, cfg, mode=RUN_ROWS, lo=None, count=False):
         """Running sums (fhe_direct_running_sum): out[p] has N slots, slot e holds the
         sum of cols[p] over the right rows j that the mode selects for left row e:
@@ -1372,6 +1428,16 @@ def group_sum_levels(key_level, cfg):
     if rc != FHE_OK:
         raise FheError(rc, lib().fhe_last_error().decode())
     return col.value, out.value
+
+
+def gather_levels(pos_level, N):
+    """fhe_gather_levels (pure host): (col_max_level, series_level, out_level) of gather
+    for positions at pos_level over N rows; the present flags end at series_level"""
+    col, ser, out = C.c_int(), C.c_int(), C.c_int()
+    rc = lib().fhe_gather_levels(int(pos_level), int(N), C.byref(col), C.byref(ser), C.byref(out))
+    if rc != FHE_OK:
+        raise FheError(rc, lib().fhe_last_error().decode())
+    return col.value, ser.value, out.value
 
 
 def window_sum_levels(key_level, nfactors, cfg):

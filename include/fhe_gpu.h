@@ -440,6 +440,68 @@ int fhe_sub_pm_const_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const 
 int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_ct *b_stack, int ncols,
                   fhe_ct **out_stack);
 
+/* Gather by encrypted position: LAG / LEAD and lookups by rank or index (the
+ * project's own extension).  pos_l and pos_r are single ciphertexts
+ * of N slots at one level holding integers in [0, N) up to the noise a rank
+ * carries, the right positions distinct; cols are ncols >= 0 single ciphertexts of
+ * N slots, offsets noffsets >= 1 public integers with |o| <= N - 1.  For column p
+ * and offset k the output holds at slot e
+ *     sum_j delta(pos_l_e + offsets[k] - pos_r_j) cols[p]_j,   j = 0 .. N - 1:
+ * the value of the right row standing offsets[k] places after left row e's
+ * position, zero where there is none (SQL's NULL, given as 0).  With pos_l = pos_r
+ * = a rank (fhe_direct_sort mode 1; with tied keys one built under
+ * fhe_set_sort_tiebreak) offset -k is LAG(v, k) and +k LEAD(v, k) in key order; with
+ * pos_r an encrypted 0 .. N - 1 and pos_l encrypted indices it is cols[p][idx].
+ * want_present != 0 appends per offset the same sum without the column: 1 where the
+ * neighbour exists.  sum_offsets != 0 adds the offsets' indicators before the
+ * product: one output per column, the sum over the offsets (a ROWS BETWEEN frame),
+ * and one present output, the frame's row count.  outs receives, in this order, the
+ * gathered columns column-major (index p K + k, K = noffsets, or p alone under
+ * sum_offsets), then the present outputs: (ncols + (want_present != 0)) * K handles.
+ * The computation is constructRank's all-pairs layout with the index check's
+ * predicate: the sort's doubled-sinc series of (pos_l_e + o - pos_r_j) / 2N, the
+ * difference negated for o < 0 so that it stays above -N, multiplied into the
+ * equally shifted column and summed over the right rows.  Levels
+ * (fhe_gather_levels): with the positions at level k the differences sit at k + 1,
+ * the series output and the present outputs at series_level, a column may sit at
+ * col_max_level = series_level - 2 at most, and the gathered columns end at
+ * out_level = series_level + 1; a rank from a level-0 key ends inside
+ * fhe_size_parameters(N)'s depth.  rots are the sort's rotation keys.  The batches
+ * run stacked in chunks of fhe_set_sort_stack / K on fhe_set_sort_lanes lanes, the
+ * columns in groups bounded by fhe_set_sort_column_members; the result does not
+ * depend on any of them, nor on fhe_set_mask_cache.  Unsharded.
+ * fhe_set_sort_tiebreak has no effect here.
+ * FHE_EINVAL (the message names the column or offset at fault) for a null
+ * position, a position or column that is a stack, slot counts that differ,
+ * positions at different levels, ncols < 0, a null column, noffsets < 1, an offset
+ * outside [-(N - 1), N - 1], and ncols == 0 without want_present; FHE_EDEPTH, before
+ * any work, for a column above col_max_level and for a context without the
+ * levels.  On failure no output handle is set (every one is NULL). */
+int fhe_direct_gather(fhe_ctx *ctx, const fhe_ct *pos_l, const fhe_ct *pos_r, const fhe_ct *const *cols, int ncols,
+                      const int32_t *offsets, int noffsets, int want_present, int sum_offsets, int N,
+                      const int32_t *rots, int nrot, fhe_ct **outs);
+/* pure host: the levels above for positions at pos_level over N rows (the series'
+ * depth taken under the default Paterson-Stockmeyer split).  Any pointer may be
+ * NULL.  FHE_EINVAL for a negative level or N < 1. */
+int fhe_gather_levels(int pos_level, int N, int *col_max_level, int *series_level, int *out_level);
+/* for tests and bindings: the oriented, offset differences, member k count + i of
+ * the noffsets count stack = fhe_add_const(fhe_sub(a, bs[i]), offsets[k]), negated
+ * (fhe_negate) for offsets[k] < 0, word for word, written by one kernel from one
+ * load of each bs[i], a loaded once per four members (FHE_GATHER_FUSED=0, read
+ * once per process: the stacked differences, then add_const / negate on the stack
+ * per offset).  The bs share a level; a at a lower level is level-adjusted once, a
+ * at a higher one takes per-member operations. */
+int fhe_sub_offsets_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const *bs, int count, const int32_t *offsets,
+                            int noffsets, fhe_ct **out);
+/* and the products they feed: a_stack holds noffsets B members (member k B + z),
+ * b_stack ncols B members column-major, all at one level; member (p noffsets + k) B
+ * + z of the result = fhe_mul_relin(member k B + z of a_stack, member p B + z of
+ * b_stack) word for word (one tensor pass that loads a column's words once per four
+ * offsets; FHE_GATHER_FUSED=0: one stacked product per column and offset).
+ * FHE_EINVAL for member counts or levels that do not fit. */
+int fhe_mul_gather(fhe_ctx *ctx, const fhe_ct *a_stack, const fhe_ct *b_stack, int ncols, int noffsets,
+                   fhe_ct **out_stack);
+
 /* Running sums: add up columns over the right rows whose key is smaller than, or
  * within a range of, the left row's (the project's own extension, like
  * fhe_direct_select and fhe_direct_group_sum).  left_key,
