@@ -106,10 +106,23 @@ int fhe_prng_block(const uint32_t key[8], uint32_t counter, const uint32_t nonce
     });
 }
 
+int fhe_params_check(const fhe_params *p, int *nq, int *K, int *alpha, int *digits) {
+    return guard([&] {
+        NEED(p);
+        const auto P = host::envelope_params(p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum);
+        if (nq) *nq = (int)P.nq();
+        if (K) *K = P.K;
+        if (alpha) *alpha = P.alpha;
+        if (digits) *digits = P.digits_at(P.nq());
+    });
+}
 int fhe_ctx_create(const fhe_params *p, int device, fhe_ctx **out) {
     return guard([&] {
         NEED(p);
         NEED(out);
+        *out = nullptr;
+        // the envelope (host/envelope.hpp), ahead of any HIP call
+        (void)host::envelope_params(p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum);
         auto c = std::make_unique<fhe_ctx>();
         c->eng = std::make_unique<Engine>(p->log_n, p->mult_depth, p->scale_bits, p->first_bits, p->dnum, device,
                                           p->seed);
@@ -1927,7 +1940,8 @@ int fhe_deserialize_context(const char *path, int device, fhe_ctx **out) {
     return guard([&] {
         NEED(path);
         NEED(out);
-        const auto p = wire::read_context(path);
+        *out = nullptr;
+        const auto p = wire::read_context(path);  // (holds the file's parameters to the envelope)
         auto c = std::make_unique<fhe_ctx>();
         c->eng = std::make_unique<Engine>(p.log_n, p.mult_depth, p.scale_bits, p.first_bits, p.dnum, device, p.seed);
         c->params = p;

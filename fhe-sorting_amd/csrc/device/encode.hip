@@ -80,7 +80,10 @@ __global__ __launch_bounds__(ENC_NT) void k_ifft_lds(double2 *v, int S, int len0
     for (int e = threadIdx.x; e < L; e += ENC_NT) g[e] = z[e];
 }
 
-__device__ __forceinline__ int brev_bits(int x, int bits) { return (int)(__brev((uint32_t)x) >> (32 - bits)); }
+// (bits = 0, one slot: the only index is 0; a shift by 32 would be undefined)
+__device__ __forceinline__ int brev_bits(int x, int bits) {
+    return bits > 0 ? (int)(__brev((uint32_t)x) >> (32 - bits)) : 0;
+}
 
 // coefficients of member b: bit reversal, / S, * scale[b], round; grid x covers n
 __global__ __launch_bounds__(256) void k_ifft_finish(const double2 *v, int64_t *coef, int S, int logS, int n,

@@ -2131,14 +2131,17 @@ __global__ __launch_bounds__(NT) void k_reduce(u64 *x, Seg S, const Mod *mods, i
 }
 
 // ------------------------------------------------------------ keyswitch ----
+constexpr int MODUP_DIGITS = fhe_envelope::MAX_DIGITS;  // what envelope_params admits at the top level
 struct ModUpArgs {
-    const u64 *qhinv[8], *qhinv_s[8], *qhat[8];  // per digit; qhat [W][qstride] (zero-padded rows)
-    int lo[8], hi[8];
+    const u64 *qhinv[MODUP_DIGITS], *qhinv_s[MODUP_DIGITS], *qhat[MODUP_DIGITS];  // per digit; qhat [W][qstride] (zero-padded rows)
+    int lo[MODUP_DIGITS], hi[MODUP_DIGITS];
     int digits, qstride;
     size_t coef_stride, ext_stride;
     // fp64 rows per digit (host::LevelTables modup_fp): [W][qstride][4], then [W][4]
-    const double *fpc[8], *fpq[8];
+    const double *fpc[MODUP_DIGITS], *fpq[MODUP_DIGITS];
 };
+static_assert(sizeof(ModUpArgs{}.lo) / sizeof(int) == fhe_envelope::MAX_DIGITS && fhe_envelope::MAX_DIGITS == 8,
+              "ModUpArgs and the dispatch_int<1, 8>(digits) tables serve the envelope's digit count");
 
 // grid: x = n / NT, y = target chunks of tch (conv_chunk), z = member * digits + digit.
 // coef: member m at m * A.coef_stride ([ell][n], coefficient form);
@@ -4097,6 +4100,10 @@ void modup_convert(u64 *ext, const u64 *coef, int ell, int K, int alpha, int dig
                    const size_t *tab_off, const Mod *mods, int logN, hipStream_t st, const double *fptab,
                    const size_t *fp_off, int fpmid) {
     const int W = ell + K;
+    // the per-digit arrays of ModUpArgs, the source loops (dispatch_int<1, 24>) and
+    // the targets: a context inside the envelope never fails here
+    if (digits < 1 || digits > MODUP_DIGITS) throw std::invalid_argument("modup_convert: 1..8 digits");
+    if (alpha < 1 || alpha > fhe_envelope::MAX_DIGIT_WIDTH) throw std::invalid_argument("modup_convert: digits of 1..24 primes");
     ModUpArgs A{};
     for (int j = 0; j < digits; ++j) {
         const u64 *base = tabs + tab_off[j];

@@ -15,6 +15,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../host/envelope.hpp"
 #include "modmath.hpp"
 
 namespace fhe {

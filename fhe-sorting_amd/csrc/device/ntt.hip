@@ -635,6 +635,11 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
     const size_t tid_global = SH ? (size_t)blockIdx.y * (NB >> F.lsegb) + (tr >> F.lsegb)
                                  : (size_t)blockIdx.y * NB + tr;  // column or row index
     const bool valid = FULL || (tid_global < ((size_t)1 << (logN - PB)) && (!SH || zseg < F.segs));
+    // the row whose twiddles this lane reads: a lane past the last row (a grid that is
+    // not FULL: the 32 rows of ring 2^10 in blocks of 64) takes row 0's, so that its
+    // indices stay inside the prime's table (its own would run up to n / 2 entries
+    // past it, past the allocation for the last prime); it loads and stores nothing
+    const size_t tw_row = (FULL || COLS || SH) ? tid_global : (valid ? tid_global : (size_t)0);
     u64 *a = data + (size_t)zseg * seg + (smap ? (size_t)__builtin_amdgcn_readfirstlane(smap[limb]) : (size_t)limb) * n;
     const u64 q = Tb.mods[p].q, q2 = 2 * q, q4 = 4 * q, nq = (u64)0 - q;
     const TW *tw;
@@ -812,7 +817,7 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
             // COLS: (t + T r0) >> (PB - s) = r0 >> (EB - s) since t < T -- a
             // compile-time index into the prime's table, so the twiddle is a
             // scalar load (constant address space) instead of 4 VGPRs
-            const size_t i = COLS ? ((size_t)r0 >> (EB - s)) : (tid_global << s) + (size_t)(idx0 >> (PB - s));
+            const size_t i = COLS ? ((size_t)r0 >> (EB - s)) : (tw_row << s) + (size_t)(idx0 >> (PB - s));
             const size_t wi = ((size_t)1 << (S0 + s)) + i;
             ct_any<FP, PB>(COLS, s, x[r0], x[r0 + (1 << hb)], (COLS && FHE_NTT_COL_SCALAR) ? scalar_tw(tw, wi) : tw[wi],
                            A);
@@ -830,7 +835,7 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
         for (int s = EB, o = 0; s < PB; ++s)
 #pragma unroll
             for (int u = 0; u < (1 << (s - EB)); ++u, ++o) {
-                const size_t i = (COLS ? 0 : (tid_global << s)) + ((size_t)t << (s - EB)) + (size_t)u;
+                const size_t i = (COLS ? 0 : (tw_row << s)) + ((size_t)t << (s - EB)) + (size_t)u;
                 tw2[PRE ? o : 0] = tw[((size_t)1 << (S0 + s)) + i];
             }
     }
@@ -868,7 +873,7 @@ __device__ __forceinline__ void ntt_fwd_body(u64 *data, size_t seg, const int *p
             for (int r0 = 0; r0 < T; ++r0) {
                 if (r0 & (1 << hb)) continue;
                 const int idx0 = (t * G + g) * T + r0;
-                const size_t i = (COLS ? 0 : (tid_global << s)) + (size_t)(idx0 >> (PB - s));
+                const size_t i = (COLS ? 0 : (tw_row << s)) + (size_t)(idx0 >> (PB - s));
                 const size_t wi = ((size_t)1 << (S0 + s)) + i;
                 const TW w = PRE ? tw2[PRE ? ((1 << (s - EB)) - 1) + (r0 >> (PB - s)) : 0] : CTW ? twc[wi] : tw[wi];
                 ct_any<FP, PB>(COLS, s, x[l2reg<G, T, SPLIT>(g, r0)], x[l2reg<G, T, SPLIT>(g, r0 + (1 << hb))], w, A);
@@ -967,6 +972,11 @@ __device__ __forceinline__ void ntt_inv_body(u64 *data, size_t seg, const int *p
     const int zseg = SH ? (int)blockIdx.x * (1 << F.lsegb) + (tr & ((1 << F.lsegb) - 1)) : (int)blockIdx.x;
     const size_t tid_global = SH ? (size_t)blockIdx.y * (NB >> F.lsegb) + (tr >> F.lsegb) : (size_t)blockIdx.y * NB + tr;
     const bool valid = FULL || (tid_global < ((size_t)1 << (logN - PB)) && (!SH || zseg < F.segs));
+    // the row whose twiddles this lane reads: a lane past the last row (a grid that is
+    // not FULL: the 32 rows of ring 2^10 in blocks of 64) takes row 0's, so that its
+    // indices stay inside the prime's table (its own would run up to n / 2 entries
+    // past it, past the allocation for the last prime); it loads and stores nothing
+    const size_t tw_row = (FULL || COLS || SH) ? tid_global : (valid ? tid_global : (size_t)0);
     u64 *a = data + (size_t)zseg * seg + (smap ? (size_t)__builtin_amdgcn_readfirstlane(smap[limb]) : (size_t)limb) * n;
     const u64 q = Tb.mods[p].q, q2 = 2 * q, q4 = 4 * q, nq = (u64)0 - q;
     const TW *tw;
@@ -1054,7 +1064,7 @@ __device__ __forceinline__ void ntt_inv_body(u64 *data, size_t seg, const int *p
         // E is a multiple of 2^(s+1), so it splits into a per-lane base and the
         // compile-time c >> (s + 1) (COLS: the column bits of idx0 << k2 vanish)
         const int sg = SG0 + s;
-        const size_t lane_base = ((COLS ? 0 : tid_global * LEN) + (size_t)t * E) >> (s + 1);
+        const size_t lane_base = ((COLS ? 0 : tw_row * LEN) + (size_t)t * E) >> (s + 1);
         const TW *tws = (CTW ? twc : tw) + (n >> (sg + 1)) + lane_base;
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -1098,7 +1108,7 @@ __device__ __forceinline__ void ntt_inv_body(u64 *data, size_t seg, const int *p
             const int r0 = ((b >> hb) << (hb + 1)) | (b & ((1 << hb) - 1));
             const int idx0 = t + T * r0;
             const int sg = SG0 + s;
-            const size_t j = COLS ? 0 : tid_global * LEN;
+            const size_t j = COLS ? 0 : tw_row * LEN;
             // COLS: i = idx0 >> (s + 1) with t < T <= 2^(s+1), i.e. (T r0) >> (s + 1):
             // a compile-time offset from a wave-uniform base -> scalar loads, no VGPRs
             const size_t i = COLS ? ((size_t)T * r0) >> (s + 1)

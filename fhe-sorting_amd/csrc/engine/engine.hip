@@ -615,20 +615,20 @@ Engine::Engine(int logN, int L, int scale_bits, int first_bits, int dnum, int de
     auto &I = *impl;
     I.device = device;
     I.seed = seed;
+    // refuses a context outside the kernels' envelope (digits, digit width,
+    // special primes, ring) before the device is touched
+    I.P = host::envelope_params(logN, L, scale_bits, first_bits, dnum);
     I.ent = host::Entropy::from_seed(seed);
     dev::install_fault_report();  // FHE_FAULT_REPORT=1 only
     HIP_OK(hipSetDevice(device));
     HIP_OK(hipStreamCreateWithFlags(&I.st, hipStreamNonBlocking));
     I.pool = std::make_shared<Pool>();
     I.pool->device = device;
-    I.P = host::make_params(logN, L, scale_bits, first_bits, dnum);
     I.LT = host::make_level_tables(I.P);
     // kernel preconditions: basis conversions hold <= 16 source residues in
     // registers and accumulate 30-bit-split products of residues < 2^60
     for (u64 q : I.P.primes)
         if (q >> 60) throw std::invalid_argument("engine: every prime must be < 2^60 (first_bits <= 60)");
-    if (I.P.alpha > 24 || I.P.K > 16)
-        throw std::invalid_argument("engine: digit size <= 24 and special primes <= 16 required (raise dnum)");
     // rescales lift the last limb with a compare-select: every prime that can be
     // rescaled away (q_1..q_L) must satisfy q_l / 2 < q_i for all Q primes
     {

@@ -153,6 +153,31 @@ Params make_params(int logN, int L, int scale_bits, int first_bits, int dnum) {
     return P;
 }
 
+Params envelope_params(int logN, int L, int scale_bits, int first_bits, int dnum) {
+    namespace E = fhe_envelope;
+    auto refuse = [](const std::string &what) { throw std::invalid_argument("context parameters out of range: " + what); };
+    if (logN < E::LOG_N_MIN || logN > E::LOG_N_MAX)
+        refuse("log_n = " + std::to_string(logN) + " outside [" + std::to_string(E::LOG_N_MIN) + ", " +
+               std::to_string(E::LOG_N_MAX) + "]");
+    if (L < 1) refuse("mult_depth = " + std::to_string(L) + " (at least 1)");
+    // make_params divides by dnum
+    if (dnum < 1) refuse("dnum = " + std::to_string(dnum) + " (at least 1)");
+    // alpha = ceil((L + 1) / dnum) sources per digit, ceil((L + 1) / alpha) digits at the top level
+    const long long alpha = ((long long)L + dnum) / dnum, digits = ((long long)L + alpha) / alpha;
+    if (digits > E::MAX_DIGITS)
+        refuse("dnum = " + std::to_string(dnum) + " gives " + std::to_string(digits) + " key-switch digits at mult_depth " +
+               std::to_string(L) + " (at most " + std::to_string(E::MAX_DIGITS) + ")");
+    if (alpha > E::MAX_DIGIT_WIDTH)
+        refuse("dnum = " + std::to_string(dnum) + " gives digits of " + std::to_string(alpha) + " primes at mult_depth " +
+               std::to_string(L) + " (at most " + std::to_string(E::MAX_DIGIT_WIDTH) + ": raise dnum)");
+    Params P = make_params(logN, L, scale_bits, first_bits, dnum);
+    if (P.alpha != alpha || P.digits_at(P.nq()) != digits) throw std::logic_error("envelope_params: digit layout");
+    if (P.K > E::MAX_SPECIAL)
+        refuse("dnum = " + std::to_string(dnum) + " needs " + std::to_string(P.K) + " special primes for digits of " +
+               std::to_string(alpha) + " primes (at most " + std::to_string(E::MAX_SPECIAL) + ": raise dnum)");
+    return P;
+}
+
 // ------------------------------------------------------------------- NTT --
 static uint32_t brev(uint32_t x, int bits) {
     uint32_t r = 0;

@@ -9,6 +9,8 @@
 #include <map>
 #include <vector>
 
+#include "envelope.hpp"
+
 namespace fhe {
 namespace host {
 
@@ -42,6 +44,11 @@ struct Params {
     int digits_at(size_t ell) const { return (int)((ell + alpha - 1) / alpha); }
 };
 Params make_params(int logN, int L, int scale_bits, int first_bits, int dnum);
+// make_params inside the envelope the kernels serve (envelope.hpp): throws
+// std::invalid_argument naming the parameter (log_n, mult_depth, dnum) for a
+// context outside it.  Host arithmetic only: the C ABI calls it ahead of any
+// HIP call, and the engine takes its parameters from it.
+Params envelope_params(int logN, int L, int scale_bits, int first_bits, int dnum);
 
 // NTT tables for one prime: psi^{brev(k)}, psi^{-brev(k)} and Shoup companions
 struct NttTable {

@@ -401,7 +401,14 @@ CtxParams read_context(const std::string &path) {
     p.seed = 0;
     if (p.log_n != (int)r.info.log_n || (uint64_t)p.mult_depth + 1 != r.info.nq)
         throw IoError(path + ": context header and body disagree");
-    // a context file drives allocations: refuse parameters no engine build uses
+    // a context file drives allocations and launches: the envelope fhe_ctx_create
+    // holds its parameters to (the refusal names the parameter), then the
+    // ranges no engine build uses
+    try {
+        (void)host::envelope_params(p.log_n, p.mult_depth, p.scale_bits, p.first_bits, p.dnum);
+    } catch (const std::invalid_argument &e) {
+        throw std::invalid_argument(path + ": " + e.what());
+    }
     if (p.log_n < 10 || p.log_n > 17 || p.mult_depth < 1 || p.mult_depth > 200 || p.scale_bits < 20 ||
         p.scale_bits > 60 || p.first_bits < 20 || p.first_bits > 60 || p.dnum < 1 || p.dnum > 64)
         throw std::invalid_argument(path + ": context parameters out of range (ring 2^" + std::to_string(p.log_n) +

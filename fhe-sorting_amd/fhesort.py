@@ -74,6 +74,7 @@ class _Hook:
 
 _SIGS = {
     'fhe_last_error': (C.c_char_p, []),
+    'fhe_params_check': (C.c_int, [C.POINTER(Params), ip, ip, ip, ip]),
     'fhe_ctx_create': (C.c_int, [C.POINTER(Params), C.c_int, PP]),
     'fhe_ctx_destroy': (C.c_int, [vp]),
     'fhe_ctx_info': (C.c_int, [vp, ip, ip, ip, u64p, dp]),
@@ -477,6 +478,16 @@ class Pt:
                 lib().fhe_pt_free(self.h)
         except Exception:
             pass
+
+
+def params_check(logN, L, scale_bits=40, first_bits=60, dnum=3):
+    """fhe_params_check: the envelope fhe_ctx_create holds a context to, on the
+    host alone.  Returns dict(nq, K, alpha, digits); raises FheError (FHE_EINVAL,
+    the parameter named) for a context the kernels cannot serve."""
+    p = Params(logN, L, scale_bits, first_bits, dnum, 0)
+    v = [C.c_int() for _ in range(4)]
+    _chk(lib().fhe_params_check(C.byref(p), *(C.byref(x) for x in v)))
+    return dict(zip(('nq', 'K', 'alpha', 'digits'), (x.value for x in v)))
 
 
 class Context:

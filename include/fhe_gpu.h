@@ -64,7 +64,23 @@ const char *fhe_last_error(void);
 int fhe_prng_block(const uint32_t key[8], uint32_t counter, const uint32_t nonce[3], uint32_t out[16]);
 
 /* ---------------------------------------------------------------- context */
-/* replaces GenCryptoContext(parameters) (tests/DirectSortTest.cpp:33) */
+/* replaces GenCryptoContext(parameters) (tests/DirectSortTest.cpp:33).
+ * The envelope: parameters the kernels cannot serve are refused with
+ * FHE_EINVAL before the device is touched, *out stays NULL and fhe_last_error
+ * names the parameter:
+ *   log_n       10..17 (the wire format's range);
+ *   mult_depth  >= 1;
+ *   dnum        >= 1, with alpha = ceil((mult_depth + 1) / dnum) primes per
+ *               digit: at most 8 digits at the top level
+ *               (ceil((mult_depth + 1) / alpha) <= 8), alpha <= 24, and at most
+ *               16 special primes (K = ceil((bits of the widest digit +
+ *               log2 alpha) / 60)) -- raise dnum when a digit is too wide;
+ *   scale_bits  20..59, first_bits scale_bits + 1 .. 60.
+ * fhe_deserialize_context holds a context file to the same envelope.
+ * fhe_params_check is the predicate alone (host arithmetic, no device): FHE_OK
+ * and the context's Q primes, special primes, digit width and top-level digit
+ * count (each pointer may be NULL), or FHE_EINVAL as above. */
+int fhe_params_check(const fhe_params *p, int *nq, int *K, int *alpha, int *digits);
 int fhe_ctx_create(const fhe_params *p, int device, fhe_ctx **out);
 int fhe_ctx_destroy(fhe_ctx *ctx);
 /* primes: nq+K values; deltas: mult_depth+1 canonical scales */

@@ -105,6 +105,7 @@ bool is_prime(u64 n) {
 
 // =============================================================== params ====
 Params make_params(int logN, int L, int scale_bits, int first_bits, int dnum) {
+    if (dnum < 1) throw std::invalid_argument("dnum must be >= 1 (alpha = ceil((L + 1) / dnum))");
     Params P;
     P.logN = logN;
     P.n = (size_t)1 << logN;
