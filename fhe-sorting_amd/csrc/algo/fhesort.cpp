@@ -41,11 +41,7 @@ void trim_zeros(std::vector<double> &a) {
 // 16 = the round-4 passes: sort 543.1 / 546.8 -> 538.2 / 537.9 ms with the window
 // kernel, profiles/r5_o; with the folded kernel 536.3 -> 523.2, profiles/r5_p)
 size_t ps_chunk() {
-    static const size_t v = [] {
-        const char *e = std::getenv("FHE_PS_CHUNK");
-        const int c = e ? std::atoi(e) : 32;
-        return (size_t)std::min(32, std::max(1, c));
-    }();
+    static const size_t v = (size_t)std::min(32, std::max(1, env_switch("FHE_PS_CHUNK", 32)));
     return v;
 }
 // FHE_MUL_FOLD_SCALARS (A/B, default 1): the a + a in front of 2 T_i T_j at equal
@@ -53,10 +49,7 @@ size_t ps_chunk() {
 // operand itself: add_mod(a, a, q) on load, the words of the separate k_add);
 // 0: the separate launch
 bool fold_scalars() {
-    static const bool v = [] {
-        const char *e = std::getenv("FHE_MUL_FOLD_SCALARS");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    static const bool v = env_switch("FHE_MUL_FOLD_SCALARS", 1);
     return v;
 }
 // FHE_LEAF_CONST_FOLD (A/B, default 1): the constant term of a rescaled
@@ -65,10 +58,7 @@ bool fold_scalars() {
 // the rescale -- a copying k_c0_op each, the leaves being views of one
 // allocation.  Same words.
 bool leaf_const_fold() {
-    static const bool v = [] {
-        const char *e = std::getenv("FHE_LEAF_CONST_FOLD");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    static const bool v = env_switch("FHE_LEAF_CONST_FOLD", 1);
     return v;
 }
 
@@ -1221,13 +1211,13 @@ DirectSortN::Lane DirectSortN::lane(int l) {
 // stream (callers sync before).  Returns each lane's partial (may be null),
 // with every lane stream drained.
 template <class F>
-std::vector<CtPtr> DirectSortN::run_lanes(const std::vector<int> &batches, F &&work) {
+auto DirectSortN::run_lanes(const std::vector<int> &batches, F &&work) {
     const int L = std::max(1, std::min(lanes, (int)batches.size()));
     std::vector<std::vector<int>> groups(L);
     for (size_t i = 0; i < batches.size(); ++i) groups[i * L / batches.size()].push_back(batches[i]);
     std::vector<Lane> ls;
     for (int l = 0; l < L; ++l) ls.push_back(lane(l));
-    std::vector<CtPtr> parts(L);
+    std::vector<decltype(work(ls[0], groups[0]))> parts(L);
     std::vector<std::exception_ptr> errs(L);
     std::vector<std::thread> th;
     for (int l = 1; l < L; ++l)
@@ -1265,10 +1255,7 @@ const Plaintext &DirectSortN::mask(Engine &E, int kind, int num_slots, int k, in
         auto it = mask_cache.find(key);
         if (it != mask_cache.end()) return *it->second;
     }
-    static const bool host_masks = [] {
-        const char *e = std::getenv("FHE_HOST_MASKS");
-        return e && std::atoi(e) == 1;
-    }();
+    static const bool host_masks = env_switch("FHE_HOST_MASKS", 0) == 1;
     PtPtr p;
     if (host_masks) {
         std::vector<double> v =
@@ -1325,10 +1312,7 @@ void reducePartial(Engine &cc, const Shard &sh, CtPtr &acc, int slots, int batch
     // from a drained stream -- this rank's compute is done -- to the reduced
     // data; the two drains that bracket it are taken only when the time is
     // wanted (FHE_TIME_COLLECTIVES=1, set by bench.py; advisor r4)
-    static const bool timed = [] {
-        const char *e = std::getenv("FHE_TIME_COLLECTIVES");
-        return e && std::atoi(e) != 0;
-    }();
+    static const bool timed = env_switch("FHE_TIME_COLLECTIVES", 0);
     if (timed) cc.sync();
     const auto t0 = std::chrono::steady_clock::now();
     auto hdr = cc.alloc_u64(4);
@@ -1419,63 +1403,47 @@ std::vector<CtPtr> DirectSortN::vecRotsOptMany(Lane L, const std::vector<CtPtr> 
 // to every difference before the sign, so equal values compare as their indices
 // do, no sign is taken at 0, and the closing constant is -1 (the self comparison
 // yields 1): the stable rank, at the same depth and levels.
+namespace {
+// acc += c, or the sum of its members
+void addMembers(Engine &E, CtPtr &acc, const Ciphertext &c) {
+    E.add_inplace(acc, c.batch == 1 ? c : *E.sum_members(c));
+}
+// `members` members of a stack from member `first` on, as a view
+Ciphertext membersOf(Engine &E, const Ciphertext &stack, int first, int members) {
+    Ciphertext v = stack;
+    v.batch = members;
+    v.data = stack.data + (size_t)first * 2 * stack.limbs * E.n();
+    return v;
+}
+}  // namespace
+
 CtPtr DirectSortN::constructRank(const Ciphertext &x, SignFunc f, const SignConfig &cfg) {
-    const SortShape s = rankShape(N, max_batch);
-    std::optional<AlgoPhase> ph;
-    ph.emplace("rank_baby");
-    std::vector<CtPtr> baby = babySteps(x, s.np);
-    for (auto &b : baby) b->slots = s.num_slots;
-    ph.reset();
-    std::vector<int> mine;
-    for (int b = 0; b < s.num_batch; ++b)
-        if (b % shard_world == shard_rank) mine.push_back(b);
-    CtPtr dup = cc.clone(x);
-    dup->slots = s.num_slots;
+    PairOp op{"rank_baby", "rank_batches", "rank_fold"};
+    op.left = op.right = {&x};
+    op.want_count = op.sharded = true;
     // tie-breaking: the offsets E_b of this rank's batches, at the level the
     // differences sit at (one masked sum's rescale below x)
-    std::map<int, PtPtr> offs;
-    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0]->level + 1, tiebreak);
-    cc.sync();  // baby steps, dup and the offsets are read by every lane
-    const size_t chunk = (size_t)std::max(1, max_stack);
-    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *L.eng;
-        AlgoPhase lane_ph("rank_batches");
-        CtPtr acc;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            std::vector<CtPtr> shifted = vecRotsOptMany(L, baby, s.num_partition, s.num_slots, s.np, iss);
-            std::vector<const Ciphertext *> ptrs;
-            for (auto &x : shifted) ptrs.push_back(x.get());
-            // x - s_b of every batch written straight into the stacked ciphertext
-            CtPtr d;
-            if (tiebreak > 0.0) {  // ... with E_b added in the same pass
-                std::vector<const Plaintext *> es;
-                for (int b : iss) es.push_back(offs.at(b).get());
-                d = E.sub_add_plain_stacked(*dup, ptrs, es);
-            } else {
-                d = ptrs.size() == 1 ? E.sub(*dup, *shifted[0]) : E.sub_stacked(*dup, ptrs);
-            }
-            shifted.clear();
-            CtPtr sg = sign(*d, E, f, cfg);
-            E.add_const_inplace(sg, 1.0);
-            CtPtr c = E.mul_const(*sg, 0.5);
-            E.add_inplace(acc, c->batch == 1 ? *c : *E.sum_members(*c));
-        }
-        return acc;
-    });
-    CtPtr rank;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(rank, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    reducePartial(rank, s.num_slots);
-    ph.emplace("rank_fold");
-    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-        rank = cc.add(*rank, *rot.rotate(*rank, s.num_slots / (1 << i)));
-    rank->slots = N;
+    op.offs_eps = tiebreak;
+    op.offs_level = x.level + 1;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        std::vector<const Ciphertext *> ptrs;
+        for (auto &s : ck.shifted) ptrs.push_back(s.get());
+        // x - s_b of every batch written straight into the stacked ciphertext
+        CtPtr d;
+        if (tiebreak > 0.0)  // ... with E_b added in the same pass
+            d = E.sub_add_plain_stacked(*ck.dups[0], ptrs, ck.offsets);
+        else
+            d = ptrs.size() == 1 ? E.sub(*ck.dups[0], *ck.shifted[0]) : E.sub_stacked(*ck.dups[0], ptrs);
+        ck.shifted.clear();
+        return sign(*d, E, f, cfg);
+    };
+    op.count = [](Engine &E, CtPtr &sg, int, CtPtr &acc) {  // compare = (sign + 1) / 2
+        E.add_const_inplace(sg, 1.0);
+        addMembers(E, acc, *E.mul_const(*sg, 0.5));
+    };
     // the self comparison: 1/2 at sign(0), a clean 1 with the tie-break offset
-    cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5);
-    return rank;
+    op.closing = [&](CtPtr &rank) { cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5); };
+    return allPairs(op)[0];
 }
 
 // E_b of the given batches from the cache; the missing ones are encoded in one
@@ -1588,8 +1556,7 @@ CtPtr DirectSortN::rotationIndexCheckN(const Ciphertext &rank, const Ciphertext 
     parts.clear();
     reducePartial(out, s.num_slots);
     AlgoPhase ph("index_fold");
-    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-        out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
+    foldPartitions(out, s);
     out->slots = N;
     return out;
 }
@@ -1620,6 +1587,145 @@ CtPtr asStack(Engine &E, const std::vector<CtPtr> &v) {
     return E.stack(p);
 }
 }  // namespace
+
+void DirectSortN::foldPartitions(CtPtr &v, const SortShape &s) {
+    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
+        v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+}
+
+std::vector<CtPtr> DirectSortN::splitMembers(const CtPtr &v, int members) {
+    std::vector<CtPtr> outs(members);
+    for (int m = 0; m < members; ++m) {
+        outs[m] = members == 1 ? v : cc.clone(*cc.member(*v, m));
+        outs[m]->slots = N;
+    }
+    return outs;
+}
+
+int DirectSortN::perProduct(size_t batches, size_t chunk, int ind_members) const {
+    // run_lanes gives a lane at most ceil(batches / lanes) batches
+    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)batches));
+    const size_t largest = std::max<size_t>(1, std::min(chunk, (batches + nl - 1) / nl));
+    return std::max(1, std::max(1, max_col_members) / (ind_members * (int)largest));
+}
+
+CtPtr DirectSortN::stackGroups(Engine &E, const std::vector<CtPtr> &accs) {
+    if (accs.size() == 1) return accs[0];
+    std::vector<const Ciphertext *> all;
+    for (auto &a : accs) all.push_back(a.get());
+    return E.stack(all);
+}
+
+void DirectSortN::checkColumns(const std::string &op, const std::string &noun,
+                               const std::vector<const Ciphertext *> &cols, int slots, int max_level) {
+    for (size_t p = 0; p < cols.size(); ++p) {
+        const std::string which = op + ": column " + std::to_string(p);
+        if (!cols[p]) throw std::invalid_argument(which + " is null");
+        if (cols[p]->batch != 1) throw std::invalid_argument(which + " is a stack");
+        if (slots >= 0 && cols[p]->slots != slots)
+            throw std::invalid_argument(which + " has " + std::to_string(cols[p]->slots) + " slots, " + noun + " " +
+                                        std::to_string(slots));
+    }
+    for (size_t p = 0; p < cols.size(); ++p)
+        if (cols[p]->level > max_level)
+            throw std::runtime_error(op + ": column " + std::to_string(p) + " at level " +
+                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
+                                     std::to_string(max_level) + "): no levels left to meet the indicator");
+}
+
+// The skeleton constructRank, lexRank, groupSums, gatherColumns, runningSums and
+// windowSums share.  Slot s of batch b pairs left row s mod N
+// with right row (s mod N + t) mod N, t = b P_ + s / N: the right operands and the
+// columns are shifted by vecRotsOpt, the operator's indicator of a chunk of
+// batches meets the equally shifted columns in one stacked product per column
+// group, and the sums over batches (exact mod q) are folded over the partitions.
+std::vector<CtPtr> DirectSortN::allPairs(const PairOp &op) {
+    const SortShape s = rankShape(N, max_batch);
+    const int P = (int)op.cols.size(), Ko = op.ind_members;
+    std::optional<AlgoPhase> ph;
+    ph.emplace(op.baby_phase);
+    auto baby_of = [&](const Ciphertext &x) {
+        std::vector<CtPtr> b = babySteps(x, s.np);
+        for (auto &c : b) c->slots = s.num_slots;
+        return b;
+    };
+    std::vector<std::vector<CtPtr>> rbaby, cbaby;
+    for (auto *r : op.right) rbaby.push_back(baby_of(*r));
+    // the columns, prepared once: scaled on the way to one level above the
+    // indicator's, then the baby steps every batch's shifted copy starts from
+    for (auto *c : op.cols) cbaby.push_back(baby_of(*cc.mul_const_to(*c, op.col_scale, op.col_level)));
+    ph.reset();
+    std::vector<int> mine;
+    for (int b = 0; b < s.num_batch; ++b)
+        if (!op.sharded || b % shard_world == shard_rank) mine.push_back(b);
+    std::vector<CtPtr> dups;
+    std::vector<const Ciphertext *> dp;
+    for (auto *l : op.left) {
+        dups.push_back(cc.clone(*l));
+        dups.back()->slots = s.num_slots;
+        dp.push_back(dups.back().get());
+    }
+    std::map<int, PtPtr> offs;
+    if (op.offs_eps > 0.0) offs = tiebreakOffsets(s.num_slots, mine, op.offs_level, op.offs_eps);
+    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
+    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / op.sign_members);
+    const int per_product = perProduct(mine.size(), chunk, Ko);
+    struct Partial {
+        CtPtr cols, cnt;
+    };
+    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> Partial {
+        Engine &E = *L.eng;
+        AlgoPhase lane_ph(op.batch_phase);
+        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
+        Partial part;
+        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
+            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
+            const int B = (int)iss.size();
+            CtPtr ind;
+            {
+                std::vector<CtPtr> shifted;  // operand-major
+                for (auto &rb : rbaby)
+                    for (auto &x : vecRotsOptMany(L, rb, s.num_partition, s.num_slots, s.np, iss)) shifted.push_back(x);
+                PairChunk ck{B, dp, shifted, {}};
+                if (!offs.empty())
+                    for (int b : iss) ck.offsets.push_back(offs.at(b).get());
+                ind = op.indicator(E, ck);
+            }
+            if (op.want_count) op.count(E, ind, B, part.cnt);
+            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
+                const int Pg = std::min(per_product, P - p0);
+                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
+                for (int p = p0; p < p0 + Pg; ++p)
+                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
+                CtPtr prod = op.product(E, *ind, B, *asStack(E, sv), Pg);
+                sv.clear();
+                E.sum_member_groups(*prod, Pg * Ko, accs[g]);
+            }
+        }
+        if (!bs.empty() && P > 0) part.cols = stackGroups(E, accs);  // the column groups, in column order
+        return part;
+    });
+    CtPtr out, cnt;
+    for (auto &p : parts)
+        if (p.cols) cc.add_inplace(out, *p.cols);
+    for (auto &p : parts)
+        if (p.cnt) cc.add_inplace(cnt, *p.cnt);
+    cc.sync();  // lane buffers return to their pools only after the main stream read them
+    parts.clear();
+    if (op.sharded) reducePartial(cnt, s.num_slots);
+    AlgoPhase fold_ph(op.fold_phase);
+    std::vector<CtPtr> outs;
+    if (P > 0) {
+        foldPartitions(out, s);
+        outs = splitMembers(out, P * Ko);
+    }
+    if (op.want_count) {
+        foldPartitions(cnt, s);
+        if (op.closing) op.closing(cnt);
+        for (auto &c : splitMembers(cnt, Ko)) outs.push_back(c);
+    }
+    return outs;
+}
 
 void DirectSortN::blindRotationColumns(Lane L, const std::vector<CtPtr> &mi, int num_slots, int np,
                                        const std::vector<int> &ibs, int P, int num_partition, CtPtr &acc) {
@@ -1656,15 +1762,7 @@ std::vector<CtPtr> DirectSortN::rotationIndexCheckColumns(const Ciphertext &rank
     const int P = (int)cols.size();
     if (P < 1) throw std::invalid_argument("sort columns: no columns");
     const int series_level = indexSeriesLevel(rank.level);
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("sort columns: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1)
-            throw std::invalid_argument("sort columns: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->level > series_level)
-            throw std::runtime_error("sort columns: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the series output (level " +
-                                     std::to_string(series_level) + "): no levels left to meet it");
-    }
+    checkColumns("sort columns", "the rank", cols, rank.slots, series_level);
     std::vector<double> idx(N);
     for (int i = 0; i < N; ++i) idx[i] = (double)i;
     PtPtr idxpt = cc.encode(idx, N, rank.level);
@@ -1685,11 +1783,7 @@ std::vector<CtPtr> DirectSortN::rotationIndexCheckColumns(const Ciphertext &rank
         if (b % shard_world == shard_rank) mine.push_back(b);
     cc.sync();  // imr and the columns are read by every lane
     const size_t chunk = (size_t)std::max(1, max_stack);
-    // columns per stacked product: the member bound over the largest chunk any
-    // lane stacks (run_lanes gives a lane at most ceil(batches / lanes) of them)
-    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
-    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
-    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
+    const int per_product = perProduct(mine.size(), chunk, 1);
     auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
         Engine &E = *L.eng;
         AlgoPhase lane_ph("index_batches");
@@ -1716,11 +1810,7 @@ std::vector<CtPtr> DirectSortN::rotationIndexCheckColumns(const Ciphertext &rank
                 blindRotationColumns(L, mi, s.num_slots, s.np, ibs, Pg, s.num_partition, accs[g]);
             }
         }
-        if (bs.empty()) return nullptr;
-        if (accs.size() == 1) return accs[0];
-        std::vector<const Ciphertext *> all;
-        for (auto &a : accs) all.push_back(a.get());
-        return E.stack(all);  // the column groups, in column order
+        return bs.empty() ? nullptr : stackGroups(E, accs);  // the column groups, in column order
     });
     CtPtr out;
     for (auto &p : parts)
@@ -1729,22 +1819,31 @@ std::vector<CtPtr> DirectSortN::rotationIndexCheckColumns(const Ciphertext &rank
     parts.clear();
     reducePartial(out, s.num_slots, P);
     AlgoPhase ph("index_fold");
-    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-        out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
-    std::vector<CtPtr> outs(P);
-    for (int p = 0; p < P; ++p) {
-        outs[p] = P == 1 ? out : cc.clone(*cc.member(*out, p));
-        outs[p]->slots = N;
-    }
-    return outs;
+    foldPartitions(out, s);
+    return splitMembers(out, P);
 }
 
 std::vector<CtPtr> DirectSortN::sortColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
                                             SignFunc f, const SignConfig &cfg) {
+    // the shape refusals before any work; the depth refusal waits for the rank's level
+    checkColumns("sort columns", "the key", cols, key.slots, std::numeric_limits<int>::max());
     if (!cache_masks) refresh_masks();
     CtPtr rank = constructRank(key, f, cfg);
     return rotationIndexCheckColumns(*rank, cols);
 }
+
+namespace {
+void checkTargets(int N, int ncols, const std::vector<int> &targets) {
+    const int k = (int)targets.size();
+    if (ncols < 1) throw std::invalid_argument("select: no columns");
+    if (k < 1 || k > N)
+        throw std::invalid_argument("select: ntargets is " + std::to_string(k) + ", need 1.." + std::to_string(N));
+    for (int p = 0; p < k; ++p)
+        if (targets[p] < 0 || targets[p] >= N)
+            throw std::invalid_argument("select: target " + std::to_string(p) + " (" + std::to_string(targets[p]) +
+                                        ") is outside [0, " + std::to_string(N) + ")");
+}
+}  // namespace
 
 // Order statistics by encrypted rank.  Slot j of sorted output is
 // sum_i x_i delta(rank_i - j); rotationIndexCheckN reaches every j by rotating x,
@@ -1757,22 +1856,9 @@ std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &rank, const std:
                                               const std::vector<int> &targets) {
     const SortShape s = rankShape(N, max_batch);
     const int P = (int)cols.size(), k = (int)targets.size();
-    if (P < 1) throw std::invalid_argument("select: no columns");
-    if (k < 1 || k > N)
-        throw std::invalid_argument("select: " + std::to_string(k) + " targets, need 1.." + std::to_string(N));
-    for (int p = 0; p < k; ++p)
-        if (targets[p] < 0 || targets[p] >= N)
-            throw std::invalid_argument("select: target " + std::to_string(p) + " (" + std::to_string(targets[p]) +
-                                        ") is outside [0, " + std::to_string(N) + ")");
+    checkTargets(N, P, targets);
     const int series_level = indexSeriesLevel(rank.level);
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("select: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1) throw std::invalid_argument("select: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->level > series_level)
-            throw std::runtime_error("select: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the series output (level " +
-                                     std::to_string(series_level) + "): no levels left to meet it");
-    }
+    checkColumns("select", "the rank", cols, rank.slots, series_level);
     const int cap = Engine::select_cap(N, s.num_slots), Z = (k + cap - 1) / cap;
     const int level_c = rank.level, level_k = series_level + 1;
     // every member's {C, K}: cached per (its targets, member, levels); with the
@@ -1846,18 +1932,15 @@ std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &rank, const std:
     for (int z = 0; z < Z; ++z) ks.push_back(pts[z][1].get());
     CtPtr out = cc.mul_plain_sum_groups(*all, ks, P);
     all.reset();
-    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-        out = cc.add(*out, *rot.rotate(*out, s.num_slots / (1 << i)));
-    std::vector<CtPtr> outs(P);
-    for (int p = 0; p < P; ++p) {
-        outs[p] = P == 1 ? out : cc.clone(*cc.member(*out, p));
-        outs[p]->slots = N;
-    }
-    return outs;
+    foldPartitions(out, s);
+    return splitMembers(out, P);
 }
 
 std::vector<CtPtr> DirectSortN::selectColumns(const Ciphertext &key, const std::vector<const Ciphertext *> &cols,
                                               const std::vector<int> &targets, SignFunc f, const SignConfig &cfg) {
+    // the shape refusals before any work; the depth refusal waits for the rank's level
+    checkTargets(N, (int)cols.size(), targets);
+    checkColumns("select", "the key", cols, key.slots, std::numeric_limits<int>::max());
     if (!cache_masks) refresh_masks();
     CtPtr rank = constructRank(key, f, cfg);
     return selectColumns(*rank, cols, targets);
@@ -1885,133 +1968,66 @@ GroupSumLevels groupSumLevels(int key_level, int n, int dg, int df, int ps_split
 // sign(d + eps) + sign(-d + eps) (2 on a match) into the indicator rides on the
 // columns' level adjustment (mul_const_to 0.5), so the count alone pays it as a
 // closing mul_const.
+namespace {
+// the two operands of a pair operator: single ciphertexts of one slot count at one level
+void checkPair(const std::string &op, const std::string &noun, const Ciphertext &l, const Ciphertext &r) {
+    if (l.batch != 1) throw std::invalid_argument(op + ": the left " + noun + " is a stack");
+    if (r.batch != 1) throw std::invalid_argument(op + ": the right " + noun + " is a stack");
+    if (l.slots != r.slots)
+        throw std::invalid_argument(op + ": the right " + noun + " has " + std::to_string(r.slots) + " slots, the left " +
+                                    noun + " " + std::to_string(l.slots));
+    if (l.level != r.level)
+        throw std::invalid_argument(op + ": the " + noun + "s sit at different levels (" + std::to_string(l.level) + ", " +
+                                    std::to_string(r.level) + ")");
+}
+void checkEps(const std::string &op, double eps) {
+    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument(op + ": eps must lie in (0, 0.5)");
+}
+void checkDepth(const std::string &op, const std::string &what, int need, int have) {
+    if (need > have)
+        throw std::runtime_error(op + ": " + what + " need " + std::to_string(need) + " levels, the context has " +
+                                 std::to_string(have) + ": no levels left");
+}
+}  // namespace
+
 std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext &kr,
                                           const std::vector<const Ciphertext *> &cols, double eps, bool want_count,
                                           SignFunc f, const SignConfig &cfg) {
-    const SortShape s = rankShape(N, max_batch);
-    const int P = (int)cols.size();
-    if (P == 0 && !want_count) throw std::invalid_argument("group sum: neither a column nor the count is asked for");
-    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("group sum: eps must lie in (0, 0.5)");
-    if (kl.batch != 1 || kr.batch != 1) throw std::invalid_argument("group sum: a key is a stack");
-    if (kl.slots != kr.slots) throw std::invalid_argument("group sum: the keys differ in slot count");
-    if (kl.level != kr.level)
-        throw std::invalid_argument("group sum: the keys sit at different levels (" + std::to_string(kl.level) + ", " +
-                                    std::to_string(kr.level) + ")");
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("group sum: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1) throw std::invalid_argument("group sum: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->slots != kl.slots)
-            throw std::invalid_argument("group sum: column " + std::to_string(p) + " has " +
-                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(kl.slots));
-    }
+    const std::string me = "group sum";
+    if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
+    checkEps(me, eps);
+    checkPair(me, "key", kl, kr);
     const GroupSumLevels lv =
         groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    if (lv.out_level > cc.params().L)
-        throw std::runtime_error("group sum: keys at level " + std::to_string(kl.level) + " need " +
-                                 std::to_string(lv.out_level) + " levels, the context has " +
-                                 std::to_string(cc.params().L) + ": no levels left");
-    for (int p = 0; p < P; ++p)
-        if (cols[p]->level > lv.col_max_level)
-            throw std::runtime_error("group sum: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
-                                     std::to_string(lv.col_max_level) + "): no levels left to meet the match indicator");
+    checkColumns(me, "the keys", cols, kl.slots, lv.col_max_level);
+    checkDepth(me, "keys at level " + std::to_string(kl.level), lv.out_level, cc.params().L);
     if (!cache_masks) refresh_masks();
-    std::optional<AlgoPhase> ph;
-    ph.emplace("group_baby");
-    std::vector<CtPtr> kbaby = babySteps(kr, s.np);
-    for (auto &b : kbaby) b->slots = s.num_slots;
-    // the columns, prepared once: halved on the way to one level above the match
-    // indicator's, then the baby steps every batch's shifted copy starts from
-    std::vector<std::vector<CtPtr>> cbaby(P);
-    for (int p = 0; p < P; ++p) {
-        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 0.5, lv.match_level - 1), s.np);
-        for (auto &b : cbaby[p]) b->slots = s.num_slots;
-    }
-    ph.reset();
-    std::vector<int> mine(s.num_batch);
-    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
-    CtPtr dup = cc.clone(kl);
-    dup->slots = s.num_slots;
-    cc.sync();  // the baby steps and dup are read by every lane
-    const size_t chunk = (size_t)std::max(1, max_stack);
-    // columns per stacked product, as rotationIndexCheckColumns bounds them
-    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
-    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
-    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
-    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level match_level)
-    std::mutex cnt_mu;
-    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *L.eng;
-        AlgoPhase lane_ph("group_batches");
-        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
-        CtPtr cnt;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            const int B = (int)iss.size();
-            CtPtr sg;
-            {
-                std::vector<CtPtr> shifted = vecRotsOptMany(L, kbaby, s.num_partition, s.num_slots, s.np, iss);
-                std::vector<const Ciphertext *> ptrs;
-                for (auto &x : shifted) ptrs.push_back(x.get());
-                // d_b + eps (members 0 .. B - 1) and -d_b + eps (members B .. 2 B - 1) of every batch
-                CtPtr d = E.sub_pm_const_stacked(*dup, ptrs, eps);
-                shifted.clear();
-                sg = sign(*d, E, f, cfg);
-            }
-            if (sg->level != lv.match_level) throw std::logic_error("group sum: unexpected sign output level");
-            Ciphertext up = *sg, dn = *sg;  // views of the two halves
-            up.batch = dn.batch = B;
-            dn.data = sg->data + (size_t)B * 2 * sg->limbs * E.n();
-            if (want_count) {
-                CtPtr m = E.add(up, dn);
-                E.add_inplace(cnt, B == 1 ? *m : *E.sum_members(*m));
-            }
-            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
-                const int Pg = std::min(per_product, P - p0);
-                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
-                for (int p = p0; p < p0 + Pg; ++p)
-                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
-                CtPtr prod = E.mul_pairs(up, dn, *asStack(E, sv), Pg);
-                sv.clear();
-                E.sum_member_groups(*prod, Pg, accs[g]);
-            }
-        }
-        if (cnt) {
-            std::lock_guard<std::mutex> lk(cnt_mu);
-            cnt_parts.push_back(cnt);
-        }
-        if (bs.empty() || P == 0) return nullptr;
-        if (accs.size() == 1) return accs[0];
-        std::vector<const Ciphertext *> all;
-        for (auto &a : accs) all.push_back(a.get());
-        return E.stack(all);  // the column groups, in column order
-    });
-    CtPtr out, cnt;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(out, *p);
-    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    cnt_parts.clear();
-    AlgoPhase fold_ph("group_fold");
-    auto fold = [&](CtPtr &v) {
-        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    PairOp op{"group_baby", "group_batches", "group_fold"};
+    op.left = {&kl};
+    op.right = {&kr};
+    op.cols = cols;
+    op.col_scale = 0.5;  // the indicator's 1/2 rides on the columns' level adjustment
+    op.col_level = lv.match_level - 1;
+    op.sign_members = 1;  // a chunk is max_stack batches, its sign a 2 B stack
+    op.want_count = want_count;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        std::vector<const Ciphertext *> ptrs;
+        for (auto &x : ck.shifted) ptrs.push_back(x.get());
+        // d_b + eps (members 0 .. B - 1) and -d_b + eps (members B .. 2 B - 1) of every batch
+        CtPtr d = E.sub_pm_const_stacked(*ck.dups[0], ptrs, eps);
+        ck.shifted.clear();
+        CtPtr sg = sign(*d, E, f, cfg);
+        if (sg->level != lv.match_level) throw std::logic_error("group sum: unexpected sign output level");
+        return sg;
     };
-    std::vector<CtPtr> outs;
-    if (P > 0) {
-        fold(out);
-        for (int p = 0; p < P; ++p) {
-            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
-            outs.back()->slots = N;
-        }
-    }
-    if (want_count) {
-        fold(cnt);
-        outs.push_back(cc.mul_const(*cnt, 0.5));
-        outs.back()->slots = N;
-    }
-    return outs;
+    op.count = [](Engine &E, CtPtr &sg, int B, CtPtr &cnt) {
+        addMembers(E, cnt, *E.add(membersOf(E, *sg, 0, B), membersOf(E, *sg, B, B)));
+    };
+    op.product = [](Engine &E, const Ciphertext &sg, int B, const Ciphertext &stack, int Pg) {
+        return E.mul_pairs(membersOf(E, sg, 0, B), membersOf(E, sg, B, B), stack, Pg);
+    };
+    op.closing = [&](CtPtr &cnt) { cnt = cc.mul_const(*cnt, 0.5); };  // the count alone pays the 1/2 itself
+    return allPairs(op);
 }
 
 GatherLevels gatherLevels(int pos_level, int N, int ps_split) {
@@ -2037,143 +2053,49 @@ GatherLevels gatherLevels(int pos_level, int N, int ps_split) {
 std::vector<CtPtr> DirectSortN::gatherColumns(const Ciphertext &pl, const Ciphertext &pr,
                                               const std::vector<const Ciphertext *> &cols,
                                               const std::vector<int> &offsets, bool want_present, bool sum_offsets) {
-    const SortShape s = rankShape(N, max_batch);
+    const std::string me = "gather";
     const int P = (int)cols.size(), K = (int)offsets.size();
-    if (P == 0 && !want_present) throw std::invalid_argument("gather: neither a column nor the present flag is asked for");
-    if (K < 1) throw std::invalid_argument("gather: no offsets");
+    if (P == 0 && !want_present) throw std::invalid_argument(me + ": neither a column nor the present flag is asked for");
+    if (K < 1) throw std::invalid_argument(me + ": no offsets (noffsets must be >= 1)");
     for (int k = 0; k < K; ++k)
         if (offsets[k] < -(N - 1) || offsets[k] > N - 1)
-            throw std::invalid_argument("gather: offset " + std::to_string(k) + " (" + std::to_string(offsets[k]) +
+            throw std::invalid_argument(me + ": offset " + std::to_string(k) + " (" + std::to_string(offsets[k]) +
                                         ") is outside [-" + std::to_string(N - 1) + ", " + std::to_string(N - 1) + "]");
-    if (pl.batch != 1 || pr.batch != 1) throw std::invalid_argument("gather: a position is a stack");
-    if (pl.slots != pr.slots) throw std::invalid_argument("gather: the positions differ in slot count");
-    if (pl.level != pr.level)
-        throw std::invalid_argument("gather: the positions sit at different levels (" + std::to_string(pl.level) + ", " +
-                                    std::to_string(pr.level) + ")");
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("gather: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1) throw std::invalid_argument("gather: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->slots != pl.slots)
-            throw std::invalid_argument("gather: column " + std::to_string(p) + " has " + std::to_string(cols[p]->slots) +
-                                        " slots, the positions " + std::to_string(pl.slots));
-    }
+    checkPair(me, "position", pl, pr);
     const GatherLevels lv = gatherLevels(pl.level, N, cc.ps_split());
-    const int need = P > 0 ? lv.out_level : lv.series_level;
-    if (need > cc.params().L)
-        throw std::runtime_error("gather: positions at level " + std::to_string(pl.level) + " need " +
-                                 std::to_string(need) + " levels, the context has " + std::to_string(cc.params().L) +
-                                 ": no levels left");
-    for (int p = 0; p < P; ++p)
-        if (cols[p]->level > lv.col_max_level)
-            throw std::runtime_error("gather: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
-                                     std::to_string(lv.col_max_level) + "): no levels left to meet the series");
+    checkColumns(me, "the positions", cols, pl.slots, lv.col_max_level);
+    checkDepth(me, "positions at level " + std::to_string(pl.level), P > 0 ? lv.out_level : lv.series_level,
+               cc.params().L);
     if (!cache_masks) refresh_masks();
-    std::optional<AlgoPhase> ph;
-    ph.emplace("gather_baby");
-    std::vector<CtPtr> rbaby = babySteps(pr, s.np);
-    for (auto &b : rbaby) b->slots = s.num_slots;
-    // the columns, prepared once: brought to one level above the series output,
-    // then the baby steps every batch's shifted copy starts from
-    std::vector<std::vector<CtPtr>> cbaby(P);
-    for (int p = 0; p < P; ++p) {
-        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 1.0, lv.series_level - 1), s.np);
-        for (auto &b : cbaby[p]) b->slots = s.num_slots;
-    }
-    ph.reset();
-    std::vector<int> mine(s.num_batch);
-    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
-    CtPtr dup = cc.clone(pl);
-    dup->slots = s.num_slots;
-    cc.sync();  // the baby steps and dup are read by every lane
-    const int Ko = sum_offsets ? 1 : K;  // indicators that meet the columns, per batch
-    // batches per stacked series: max_stack members over the K offsets
-    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / K);
-    // columns per stacked product, as rotationIndexCheckColumns bounds them
-    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
-    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
-    const int per_product = std::max(1, std::max(1, max_col_members) / (Ko * (int)largest));
     const std::vector<double> &coeffs = sincCoefficients();
-    std::vector<CtPtr> cnt_parts;  // every lane's present partial (level series_level)
-    std::mutex cnt_mu;
-    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *L.eng;
-        AlgoPhase lane_ph("gather_batches");
-        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
-        CtPtr cnt;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            const int B = (int)iss.size();
-            CtPtr r;
-            {
-                std::vector<CtPtr> shifted = vecRotsOptMany(L, rbaby, s.num_partition, s.num_slots, s.np, iss);
-                std::vector<const Ciphertext *> ptrs;
-                for (auto &x : shifted) ptrs.push_back(x.get());
-                CtPtr d = E.sub_offsets_stacked(*dup, ptrs, offsets);  // member k B + z
-                shifted.clear();
-                r = evalChebyshevSeriesPS(E, *E.mul_const(*d, 1.0 / N / 2), coeffs, -1.0, 1.0);
-            }
-            if (r->level != lv.series_level) throw std::logic_error("gather: unexpected series output level");
-            if (sum_offsets && K > 1) {  // the frame: the offsets' indicators added, exact mod q
-                const size_t words = (size_t)B * 2 * r->limbs * E.n();
-                Ciphertext v = *r;
-                v.batch = B;
-                CtPtr sum = E.clone(v);
-                for (int k = 1; k < K; ++k) {
-                    v.data = r->data + (size_t)k * words;
-                    E.add_inplace(sum, v);
-                }
-                r = sum;
-            }
-            if (want_present) E.sum_member_groups(*r, Ko, cnt);
-            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
-                const int Pg = std::min(per_product, P - p0);
-                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
-                for (int p = p0; p < p0 + Pg; ++p)
-                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
-                CtPtr prod = E.mul_gather(*r, *asStack(E, sv), Pg, Ko);  // member ((p - p0) Ko + k) B + z
-                sv.clear();
-                E.sum_member_groups(*prod, Pg * Ko, accs[g]);
-            }
+    PairOp op{"gather_baby", "gather_batches", "gather_fold"};
+    op.left = {&pl};
+    op.right = {&pr};
+    op.cols = cols;
+    op.col_level = lv.series_level - 1;  // one level above the series output
+    op.sign_members = K;                 // a batch's series runs over its K offsets
+    op.ind_members = sum_offsets ? 1 : K;
+    op.want_count = want_present;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        std::vector<const Ciphertext *> ptrs;
+        for (auto &x : ck.shifted) ptrs.push_back(x.get());
+        CtPtr d = E.sub_offsets_stacked(*ck.dups[0], ptrs, offsets);  // member k B + z
+        ck.shifted.clear();
+        CtPtr r = evalChebyshevSeriesPS(E, *E.mul_const(*d, 1.0 / N / 2), coeffs, -1.0, 1.0);
+        d.reset();
+        if (r->level != lv.series_level) throw std::logic_error("gather: unexpected series output level");
+        if (sum_offsets && K > 1) {  // the frame: the offsets' indicators added, exact mod q
+            CtPtr sum = E.clone(membersOf(E, *r, 0, ck.B));
+            for (int k = 1; k < K; ++k) E.add_inplace(sum, membersOf(E, *r, k * ck.B, ck.B));
+            r = sum;
         }
-        if (cnt) {
-            std::lock_guard<std::mutex> lk(cnt_mu);
-            cnt_parts.push_back(cnt);
-        }
-        if (bs.empty() || P == 0) return nullptr;
-        if (accs.size() == 1) return accs[0];
-        std::vector<const Ciphertext *> all;
-        for (auto &a : accs) all.push_back(a.get());
-        return E.stack(all);  // the column groups, in column order
-    });
-    CtPtr out, cnt;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(out, *p);
-    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    cnt_parts.clear();
-    AlgoPhase fold_ph("gather_fold");
-    auto fold = [&](CtPtr &v) {
-        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+        return r;
     };
-    std::vector<CtPtr> outs;
-    if (P > 0) {
-        fold(out);
-        for (int m = 0; m < P * Ko; ++m) {
-            outs.push_back(P * Ko == 1 ? out : cc.clone(*cc.member(*out, m)));
-            outs.back()->slots = N;
-        }
-    }
-    if (want_present) {
-        fold(cnt);
-        for (int k = 0; k < Ko; ++k) {
-            outs.push_back(Ko == 1 ? cnt : cc.clone(*cc.member(*cnt, k)));
-            outs.back()->slots = N;
-        }
-    }
-    return outs;
+    op.count = [&](Engine &E, CtPtr &r, int, CtPtr &cnt) { E.sum_member_groups(*r, op.ind_members, cnt); };
+    op.product = [&](Engine &E, const Ciphertext &r, int, const Ciphertext &stack, int Pg) {
+        return E.mul_gather(r, stack, Pg, op.ind_members);  // member ((p - p0) Ko + k) B + z
+    };
+    return allPairs(op);
 }
 
 // Running sums.  groupSums' layout with the rank's own predicate: slot s of batch b
@@ -2186,158 +2108,68 @@ std::vector<CtPtr> DirectSortN::gatherColumns(const Ciphertext &pl, const Cipher
 std::vector<CtPtr> DirectSortN::runningSums(const Ciphertext &kl, const Ciphertext *lo, const Ciphertext &kr,
                                             const std::vector<const Ciphertext *> &cols, int mode, double eps,
                                             bool want_count, SignFunc f, const SignConfig &cfg) {
-    const SortShape s = rankShape(N, max_batch);
-    const int P = (int)cols.size();
+    const std::string me = "running sum";
     if (mode < RunRows || mode > RunBetween)
-        throw std::invalid_argument("running sum: mode must lie in 0..3, got " + std::to_string(mode));
-    if (mode == RunBetween && !lo) throw std::invalid_argument("running sum: the between mode needs the lower bound");
-    if (mode != RunBetween && lo) throw std::invalid_argument("running sum: a lower bound is given outside the between mode");
-    if (P == 0 && !want_count) throw std::invalid_argument("running sum: neither a column nor the count is asked for");
-    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("running sum: eps must lie in (0, 0.5)");
-    if (kl.batch != 1 || kr.batch != 1) throw std::invalid_argument("running sum: a key is a stack");
-    if (kl.slots != kr.slots) throw std::invalid_argument("running sum: the keys differ in slot count");
-    if (kl.level != kr.level)
-        throw std::invalid_argument("running sum: the keys sit at different levels (" + std::to_string(kl.level) + ", " +
-                                    std::to_string(kr.level) + ")");
+        throw std::invalid_argument(me + ": mode must lie in 0..3, got " + std::to_string(mode));
+    if (mode == RunBetween && !lo) throw std::invalid_argument(me + ": the between mode needs left_lo, the lower bound");
+    if (mode != RunBetween && lo) throw std::invalid_argument(me + ": left_lo, a lower bound, is given outside the between mode");
+    if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
+    checkEps(me, eps);
+    checkPair(me, "key", kl, kr);
     if (lo) {
-        if (lo->batch != 1) throw std::invalid_argument("running sum: the lower bound is a stack");
-        if (lo->slots != kl.slots) throw std::invalid_argument("running sum: the lower bound differs in slot count");
+        if (lo->batch != 1) throw std::invalid_argument(me + ": left_lo, the lower bound, is a stack");
+        if (lo->slots != kl.slots)
+            throw std::invalid_argument(me + ": left_lo, the lower bound, has " + std::to_string(lo->slots) +
+                                        " slots, the left key " + std::to_string(kl.slots));
         if (lo->level != kl.level || lo->limbs != kl.limbs)
-            throw std::invalid_argument("running sum: the lower bound sits at another level (" +
-                                        std::to_string(lo->level) + ", the keys at " + std::to_string(kl.level) + ")");
-    }
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("running sum: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1) throw std::invalid_argument("running sum: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->slots != kl.slots)
-            throw std::invalid_argument("running sum: column " + std::to_string(p) + " has " +
-                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(kl.slots));
+            throw std::invalid_argument(me + ": left_lo, the lower bound, sits at level " + std::to_string(lo->level) +
+                                        ", the keys at " + std::to_string(kl.level));
     }
     const GroupSumLevels lv =
         groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    if (lv.out_level > cc.params().L)
-        throw std::runtime_error("running sum: keys at level " + std::to_string(kl.level) + " need " +
-                                 std::to_string(lv.out_level) + " levels, the context has " +
-                                 std::to_string(cc.params().L) + ": no levels left");
-    for (int p = 0; p < P; ++p)
-        if (cols[p]->level > lv.col_max_level)
-            throw std::runtime_error("running sum: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
-                                     std::to_string(lv.col_max_level) + "): no levels left to meet the indicator");
+    checkColumns(me, "the keys", cols, kl.slots, lv.col_max_level);
+    checkDepth(me, "keys at level " + std::to_string(kl.level), lv.out_level, cc.params().L);
     if (!cache_masks) refresh_masks();
-    std::optional<AlgoPhase> ph;
-    ph.emplace("run_baby");
-    std::vector<CtPtr> kbaby = babySteps(kr, s.np);
-    for (auto &b : kbaby) b->slots = s.num_slots;
-    // the columns, prepared as groupSums prepares them (the same cached masks serve both)
-    std::vector<std::vector<CtPtr>> cbaby(P);
-    for (int p = 0; p < P; ++p) {
-        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 0.5, lv.match_level - 1), s.np);
-        for (auto &b : cbaby[p]) b->slots = s.num_slots;
-    }
-    ph.reset();
-    std::vector<int> mine(s.num_batch);
-    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
-    CtPtr dup = cc.clone(kl), dup_lo;
-    dup->slots = s.num_slots;
-    if (lo) {
-        dup_lo = cc.clone(*lo);
-        dup_lo->slots = s.num_slots;
-    }
+    const bool between = mode == RunBetween;
+    PairOp op{"run_baby", "run_batches", "run_fold"};
+    op.left = {&kl};
+    if (lo) op.left.push_back(lo);
+    op.right = {&kr};
+    op.cols = cols;
+    op.col_scale = 0.5;  // prepared as groupSums prepares them (the same cached masks serve both)
+    op.col_level = lv.match_level - 1;
+    op.sign_members = between ? 2 : 1;
+    op.want_count = want_count;
     // RunRows: the offsets E_b of this call's eps, at the level the differences sit at
-    std::map<int, PtPtr> offs;
-    if (mode == RunRows) offs = tiebreakOffsets(s.num_slots, mine, lv.diff_level, eps);
-    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
-    const int per_batch = mode == RunBetween ? 2 : 1;  // sign members per batch
-    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / per_batch);
-    // columns per stacked product, as rotationIndexCheckColumns bounds them
-    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
-    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
-    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
-    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level match_level + 1)
-    std::mutex cnt_mu;
-    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *L.eng;
-        AlgoPhase lane_ph("run_batches");
-        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
-        CtPtr cnt;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            const int B = (int)iss.size();
-            CtPtr sg;
-            {
-                std::vector<CtPtr> shifted = vecRotsOptMany(L, kbaby, s.num_partition, s.num_slots, s.np, iss);
-                std::vector<const Ciphertext *> ptrs;
-                for (auto &x : shifted) ptrs.push_back(x.get());
-                CtPtr d;
-                if (mode == RunRows) {  // d_b + E_b, the rank's own tie-broken differences
-                    std::vector<const Plaintext *> es;
-                    for (int b : iss) es.push_back(offs.at(b).get());
-                    d = E.sub_add_plain_stacked(*dup, ptrs, es);
-                } else if (mode == RunBetween) {  // hi - s_b + eps (members 0 .. B - 1), lo - s_b - eps (B .. 2 B - 1)
-                    d = E.sub_bounds_stacked({dup.get(), dup_lo.get()}, ptrs, {eps, -eps});
-                } else {
-                    d = E.sub_bounds_stacked({dup.get()}, ptrs, {mode == RunLE ? eps : -eps});
-                }
-                shifted.clear();
-                sg = sign(*d, E, f, cfg);
-            }
-            if (sg->level != lv.match_level) throw std::logic_error("running sum: unexpected sign output level");
-            Ciphertext up = *sg, dn = *sg;  // RunBetween: views of the two halves
-            up.batch = dn.batch = B;
-            if (mode == RunBetween) dn.data = sg->data + (size_t)B * 2 * sg->limbs * E.n();
-            if (want_count) {  // the indicator is written out only here
-                CtPtr a = mode == RunBetween ? E.sub(up, dn) : E.add_const(up, 1.0);
-                CtPtr c = E.mul_const(*a, 0.5);
-                E.add_inplace(cnt, B == 1 ? *c : *E.sum_members(*c));
-            }
-            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
-                const int Pg = std::min(per_product, P - p0);
-                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
-                for (int p = p0; p < p0 + Pg; ++p)
-                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
-                CtPtr prod = mode == RunBetween ? E.mul_pairs_sub(up, dn, *asStack(E, sv), Pg)
-                                                : E.mul_pairs_const(up, 1.0, *asStack(E, sv), Pg);
-                sv.clear();
-                E.sum_member_groups(*prod, Pg, accs[g]);
-            }
-        }
-        if (cnt) {
-            std::lock_guard<std::mutex> lk(cnt_mu);
-            cnt_parts.push_back(cnt);
-        }
-        if (bs.empty() || P == 0) return nullptr;
-        if (accs.size() == 1) return accs[0];
-        std::vector<const Ciphertext *> all;
-        for (auto &a : accs) all.push_back(a.get());
-        return E.stack(all);  // the column groups, in column order
-    });
-    CtPtr out, cnt;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(out, *p);
-    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    cnt_parts.clear();
-    AlgoPhase fold_ph("run_fold");
-    auto fold = [&](CtPtr &v) {
-        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+    op.offs_eps = mode == RunRows ? eps : 0.0;
+    op.offs_level = lv.diff_level;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        std::vector<const Ciphertext *> ptrs;
+        for (auto &x : ck.shifted) ptrs.push_back(x.get());
+        CtPtr d;
+        if (mode == RunRows)  // d_b + E_b, the rank's own tie-broken differences
+            d = E.sub_add_plain_stacked(*ck.dups[0], ptrs, ck.offsets);
+        else if (between)  // hi - s_b + eps (members 0 .. B - 1), lo - s_b - eps (B .. 2 B - 1)
+            d = E.sub_bounds_stacked(ck.dups, ptrs, {eps, -eps});
+        else
+            d = E.sub_bounds_stacked(ck.dups, ptrs, {mode == RunLE ? eps : -eps});
+        ck.shifted.clear();
+        CtPtr sg = sign(*d, E, f, cfg);
+        if (sg->level != lv.match_level) throw std::logic_error("running sum: unexpected sign output level");
+        return sg;
     };
-    std::vector<CtPtr> outs;
-    if (P > 0) {
-        fold(out);
-        for (int p = 0; p < P; ++p) {
-            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
-            outs.back()->slots = N;
-        }
-    }
-    if (want_count) {
-        fold(cnt);
-        outs.push_back(cnt);
-        outs.back()->slots = N;
-    }
-    return outs;
+    // the indicator s + 1 (u - w between two bounds) is written out only for the
+    // count, halved per batch as constructRank's compare is
+    op.count = [&](Engine &E, CtPtr &sg, int B, CtPtr &cnt) {
+        const Ciphertext up = membersOf(E, *sg, 0, B);
+        CtPtr a = between ? E.sub(up, membersOf(E, *sg, B, B)) : E.add_const(up, 1.0);
+        addMembers(E, cnt, *E.mul_const(*a, 0.5));
+    };
+    op.product = [&](Engine &E, const Ciphertext &sg, int B, const Ciphertext &stack, int Pg) {
+        const Ciphertext up = membersOf(E, sg, 0, B);
+        return between ? E.mul_pairs_sub(up, membersOf(E, sg, B, B), stack, Pg) : E.mul_pairs_const(up, 1.0, stack, Pg);
+    };
+    return allPairs(op);
 }
 
 WindowSumLevels windowSumLevels(int key_level, int nfactors, int n, int dg, int df, int ps_split) {
@@ -2364,23 +2196,23 @@ std::vector<CtPtr> DirectSortN::windowSums(const std::vector<const Ciphertext *>
                                            const Ciphertext *olo, const Ciphertext *orr,
                                            const std::vector<const Ciphertext *> &cols, int mode, double eps,
                                            bool want_count, SignFunc f, const SignConfig &cfg) {
-    const SortShape s = rankShape(N, max_batch);
-    const int P = (int)cols.size(), G = (int)pl.size();
+    const std::string me = "window sum";
+    const int G = (int)pl.size();
     if (mode < WinRows || mode > WinGroup)
-        throw std::invalid_argument("window sum: mode must lie in 0..4, got " + std::to_string(mode));
-    if (G < 1 || G > 3) throw std::invalid_argument("window sum: 1 to 3 partition keys, got " + std::to_string(G));
-    if ((int)pr.size() != G) throw std::invalid_argument("window sum: one right partition key per left one");
+        throw std::invalid_argument(me + ": mode must lie in 0..4, got " + std::to_string(mode));
+    if (G < 1 || G > 3) throw std::invalid_argument(me + ": nparts must lie in 1..3, got " + std::to_string(G));
+    if ((int)pr.size() != G) throw std::invalid_argument(me + ": one right partition key per left one");
     const int F = G + (mode != WinGroup ? 1 : 0);
-    if (F < 2) throw std::invalid_argument("window sum: one partition key without an order key is the group sum");
-    if (F > 4) throw std::invalid_argument("window sum: at most 4 factors, got " + std::to_string(F));
+    if (F < 2) throw std::invalid_argument(me + ": one partition key without an order key is the group sum, fhe_direct_group_sum");
+    if (F > 4) throw std::invalid_argument(me + ": at most 4 factors, got " + std::to_string(F));
     if (mode == WinGroup && (ol || orr || olo))
-        throw std::invalid_argument("window sum: an order key is given in the group mode");
-    if (mode != WinGroup && (!ol || !orr)) throw std::invalid_argument("window sum: the mode needs the order key");
-    if (mode == WinBetween && !olo) throw std::invalid_argument("window sum: the between mode needs the lower bound");
+        throw std::invalid_argument(me + ": an order key is given in the group mode");
+    if (mode != WinGroup && (!ol || !orr)) throw std::invalid_argument(me + ": the mode needs the order key");
+    if (mode == WinBetween && !olo) throw std::invalid_argument(me + ": the between mode needs order_lo, the lower bound");
     if (mode != WinBetween && olo)
-        throw std::invalid_argument("window sum: a lower bound is given outside the between mode");
-    if (P == 0 && !want_count) throw std::invalid_argument("window sum: neither a column nor the count is asked for");
-    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("window sum: eps must lie in (0, 0.5)");
+        throw std::invalid_argument(me + ": order_lo, a lower bound, is given outside the between mode");
+    if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
+    checkEps(me, eps);
     std::vector<std::pair<std::string, const Ciphertext *>> keys;
     for (int g = 0; g < G; ++g) {
         keys.emplace_back("left partition key " + std::to_string(g), pl[g]);
@@ -2389,179 +2221,78 @@ std::vector<CtPtr> DirectSortN::windowSums(const std::vector<const Ciphertext *>
     if (ol) keys.emplace_back("left order key", ol);
     if (orr) keys.emplace_back("right order key", orr);
     if (olo) keys.emplace_back("lower bound", olo);
+    for (auto &k : keys)
+        if (!k.second) throw std::invalid_argument(me + ": the " + k.first + " is null");
     for (auto &k : keys) {
-        if (!k.second) throw std::invalid_argument("window sum: the " + k.first + " is null");
-        if (k.second->batch != 1) throw std::invalid_argument("window sum: the " + k.first + " is a stack");
+        if (k.second->batch != 1) throw std::invalid_argument(me + ": the " + k.first + " is a stack");
         if (k.second->slots != N)
-            throw std::invalid_argument("window sum: the " + k.first + " has " + std::to_string(k.second->slots) +
+            throw std::invalid_argument(me + ": the " + k.first + " has " + std::to_string(k.second->slots) +
                                         " slots, need " + std::to_string(N));
         if (k.second->level != pl[0]->level || k.second->limbs != pl[0]->limbs)
-            throw std::invalid_argument("window sum: the keys sit at different levels (the " + k.first + " at " +
+            throw std::invalid_argument(me + ": the keys sit at different levels (the " + k.first + " at " +
                                         std::to_string(k.second->level) + ", left partition key 0 at " +
                                         std::to_string(pl[0]->level) + ")");
     }
-    for (int p = 0; p < P; ++p) {
-        if (!cols[p]) throw std::invalid_argument("window sum: column " + std::to_string(p) + " is null");
-        if (cols[p]->batch != 1) throw std::invalid_argument("window sum: column " + std::to_string(p) + " is a stack");
-        if (cols[p]->slots != N)
-            throw std::invalid_argument("window sum: column " + std::to_string(p) + " has " +
-                                        std::to_string(cols[p]->slots) + " slots, the keys " + std::to_string(N));
-    }
     const WindowSumLevels lv =
         windowSumLevels(pl[0]->level, F, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    if (lv.out_level > cc.params().L)
-        throw std::runtime_error("window sum: " + std::to_string(F) + " factors on keys at level " +
-                                 std::to_string(pl[0]->level) + " need " + std::to_string(lv.out_level) +
-                                 " levels, the context has " + std::to_string(cc.params().L) + ": no levels left");
-    for (int p = 0; p < P; ++p)
-        if (cols[p]->level > lv.col_max_level)
-            throw std::runtime_error("window sum: column " + std::to_string(p) + " at level " +
-                                     std::to_string(cols[p]->level) + " is below the deepest a column may sit at (level " +
-                                     std::to_string(lv.col_max_level) + "): no levels left to meet the indicator");
+    checkColumns(me, "the keys", cols, N, lv.col_max_level);
+    checkDepth(me, std::to_string(F) + " factors on keys at level " + std::to_string(pl[0]->level), lv.out_level,
+               cc.params().L);
     if (!cache_masks) refresh_masks();
-    std::optional<AlgoPhase> ph;
-    ph.emplace("win_baby");
-    const int K = G + (orr ? 1 : 0);  // right keys to shift: the partition keys, then the order key
-    std::vector<std::vector<CtPtr>> kbaby(K);
-    for (int k = 0; k < K; ++k) {
-        kbaby[k] = babySteps(k < G ? *pr[k] : *orr, s.np);
-        for (auto &b : kbaby[k]) b->slots = s.num_slots;
-    }
-    // the columns, prepared as groupSums prepares them: 2^-F on the way to the level below the indicators' product
-    std::vector<std::vector<CtPtr>> cbaby(P);
-    for (int p = 0; p < P; ++p) {
-        cbaby[p] = babySteps(*cc.mul_const_to(*cols[p], 1.0 / (double)(1 << F), lv.prod_level - 1), s.np);
-        for (auto &b : cbaby[p]) b->slots = s.num_slots;
-    }
-    ph.reset();
-    std::vector<int> mine(s.num_batch);
-    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
-    auto dup_of = [&](const Ciphertext &x) {
-        CtPtr d = cc.clone(x);
-        d->slots = s.num_slots;
-        return d;
-    };
-    std::vector<CtPtr> dups;
-    std::vector<const Ciphertext *> dp;
-    for (int g = 0; g < G; ++g) {
-        dups.push_back(dup_of(*pl[g]));
-        dp.push_back(dups.back().get());
-    }
-    CtPtr dup_o = ol ? dup_of(*ol) : nullptr, dup_lo = olo ? dup_of(*olo) : nullptr;
-    // WinRows: the offsets E_b of this call's eps, at the level the differences sit at
-    std::map<int, PtPtr> offs;
-    if (mode == WinRows) offs = tiebreakOffsets(s.num_slots, mine, lv.diff_level, eps);
-    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
     const int V = mode == WinGroup ? 0 : mode == WinBetween ? 2 : 1;  // the order key's sign members per batch
-    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / (2 * G + V));
-    // columns per stacked product, as rotationIndexCheckColumns bounds them
-    const size_t nl = (size_t)std::max(1, std::min(lanes, (int)mine.size()));
-    const size_t largest = std::max<size_t>(1, std::min(chunk, (mine.size() + nl - 1) / nl));
-    const int per_product = std::max(1, std::max(1, max_col_members) / (int)largest);
     const double scale_down = 1.0 / (double)(1 << F);
-    std::vector<CtPtr> cnt_parts;  // every lane's count partial (level prod_level + 1)
-    std::mutex cnt_mu;
-    auto parts = run_lanes(mine, [&](Lane L, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *L.eng;
-        AlgoPhase lane_ph("win_batches");
-        std::vector<CtPtr> accs((P + per_product - 1) / per_product);
-        CtPtr cnt;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            const int B = (int)iss.size();
-            CtPtr sg;
-            {
-                std::vector<CtPtr> shifted;  // key-major: the partition keys, then the order key
-                for (int k = 0; k < K; ++k)
-                    for (auto &x : vecRotsOptMany(L, kbaby[k], s.num_partition, s.num_slots, s.np, iss))
-                        shifted.push_back(x);
-                std::vector<const Ciphertext *> pb, ob;
-                for (int i = 0; i < G * B; ++i) pb.push_back(shifted[(size_t)i].get());
-                for (int i = G * B; i < K * B; ++i) ob.push_back(shifted[(size_t)i].get());
-                std::vector<const Plaintext *> es;
-                if (mode == WinRows)
-                    for (int b : iss) es.push_back(offs.at(b).get());
-                CtPtr d = E.sub_window_stacked(dp, pb, dup_o.get(), dup_lo.get(), ob, es, mode == WinLT ? -eps : eps, eps);
-                shifted.clear();
-                sg = sign(*d, E, f, cfg);
-            }
-            if (sg->level != lv.match_level) throw std::logic_error("window sum: unexpected sign output level");
-            auto view = [&](int first) {  // B members of the sign's stack from member `first` on
-                Ciphertext v = *sg;
-                v.batch = B;
-                v.data = sg->data + (size_t)first * 2 * sg->limbs * E.n();
-                return v;
-            };
-            // M_g R: (u_g - w_g) (s + 1), or (u_g - w_g) (u' - w') between two bounds
-            auto withOrder = [&](int g) {
-                const Ciphertext u = view(2 * g * B), w = view((2 * g + 1) * B), so = view(2 * G * B);
-                return mode == WinBetween ? E.mul_sub_sub(u, w, so, view((2 * G + 1) * B)) : E.mul_lex(so, 1.0, u, w);
-            };
-            auto twoKeys = [&](int g, int h) {  // M_g M_h
-                return E.mul_sub_sub(view(2 * g * B), view((2 * g + 1) * B), view(2 * h * B), view((2 * h + 1) * B));
-            };
-            CtPtr A;
-            if (F == 2) {
-                A = mode == WinGroup ? twoKeys(0, 1) : withOrder(0);
-            } else if (F == 3) {  // M_0 meets the inner product one level above it: sub, then the product adjusts it
-                CtPtr inner = mode == WinGroup ? twoKeys(1, 2) : withOrder(1);
-                A = E.mul(*E.sub(view(0), view(B)), *inner);
-            } else {
-                CtPtr left = twoKeys(0, 1), right = withOrder(2);
-                A = E.mul(*left, *right);
-            }
-            if (A->level != lv.prod_level) throw std::logic_error("window sum: unexpected indicator level");
-            if (want_count) {
-                CtPtr c = E.mul_const(*A, scale_down);
-                E.add_inplace(cnt, B == 1 ? *c : *E.sum_members(*c));
-            }
-            for (int p0 = 0, g = 0; p0 < P; p0 += per_product, ++g) {
-                const int Pg = std::min(per_product, P - p0);
-                std::vector<CtPtr> sv;  // column-major: member (p - p0) B + z
-                for (int p = p0; p < p0 + Pg; ++p)
-                    for (auto &x : vecRotsOptMany(L, cbaby[p], s.num_partition, s.num_slots, s.np, iss)) sv.push_back(x);
-                // the stacked column product with nothing added to the indicator: mul(A_z, column)'s words
-                CtPtr prod = E.mul_pairs_const(*A, 0.0, *asStack(E, sv), Pg);
-                sv.clear();
-                E.sum_member_groups(*prod, Pg, accs[g]);
-            }
+    PairOp op{"win_baby", "win_batches", "win_fold"};
+    op.left = pl;  // the partition keys, then the order key and its lower bound
+    if (ol) op.left.push_back(ol);
+    if (olo) op.left.push_back(olo);
+    op.right = pr;
+    if (orr) op.right.push_back(orr);
+    op.cols = cols;
+    op.col_scale = scale_down;  // 2^-F on the way to the level below the indicators' product
+    op.col_level = lv.prod_level - 1;
+    op.sign_members = 2 * G + V;
+    op.want_count = want_count;
+    // WinRows: the offsets E_b of this call's eps, at the level the differences sit at
+    op.offs_eps = mode == WinRows ? eps : 0.0;
+    op.offs_level = lv.diff_level;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        const int B = ck.B;
+        std::vector<const Ciphertext *> dp(ck.dups.begin(), ck.dups.begin() + G), pb, ob;
+        for (size_t i = 0; i < ck.shifted.size(); ++i) (i < (size_t)(G * B) ? pb : ob).push_back(ck.shifted[i].get());
+        CtPtr d = E.sub_window_stacked(dp, pb, ol ? ck.dups[G] : nullptr, olo ? ck.dups[G + 1] : nullptr, ob, ck.offsets,
+                                       mode == WinLT ? -eps : eps, eps);
+        ck.shifted.clear();
+        CtPtr sg = sign(*d, E, f, cfg);
+        d.reset();
+        if (sg->level != lv.match_level) throw std::logic_error("window sum: unexpected sign output level");
+        auto view = [&](int first) { return membersOf(E, *sg, first, B); };
+        // M_g R: (u_g - w_g) (s + 1), or (u_g - w_g) (u' - w') between two bounds
+        auto withOrder = [&](int g) {
+            const Ciphertext u = view(2 * g * B), w = view((2 * g + 1) * B), so = view(2 * G * B);
+            return mode == WinBetween ? E.mul_sub_sub(u, w, so, view((2 * G + 1) * B)) : E.mul_lex(so, 1.0, u, w);
+        };
+        auto twoKeys = [&](int g, int h) {  // M_g M_h
+            return E.mul_sub_sub(view(2 * g * B), view((2 * g + 1) * B), view(2 * h * B), view((2 * h + 1) * B));
+        };
+        CtPtr A;
+        if (F == 2) {
+            A = mode == WinGroup ? twoKeys(0, 1) : withOrder(0);
+        } else if (F == 3) {  // M_0 meets the inner product one level above it: sub, then the product adjusts it
+            CtPtr inner = mode == WinGroup ? twoKeys(1, 2) : withOrder(1);
+            A = E.mul(*E.sub(view(0), view(B)), *inner);
+        } else {
+            CtPtr left = twoKeys(0, 1), right = withOrder(2);
+            A = E.mul(*left, *right);
         }
-        if (cnt) {
-            std::lock_guard<std::mutex> lk(cnt_mu);
-            cnt_parts.push_back(cnt);
-        }
-        if (bs.empty() || P == 0) return nullptr;
-        if (accs.size() == 1) return accs[0];
-        std::vector<const Ciphertext *> all;
-        for (auto &a : accs) all.push_back(a.get());
-        return E.stack(all);  // the column groups, in column order
-    });
-    CtPtr out, cnt;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(out, *p);
-    for (auto &p : cnt_parts) cc.add_inplace(cnt, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    cnt_parts.clear();
-    AlgoPhase fold_ph("win_fold");
-    auto fold = [&](CtPtr &v) {
-        for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-            v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
+        if (A->level != lv.prod_level) throw std::logic_error("window sum: unexpected indicator level");
+        return A;
     };
-    std::vector<CtPtr> outs;
-    if (P > 0) {
-        fold(out);
-        for (int p = 0; p < P; ++p) {
-            outs.push_back(P == 1 ? out : cc.clone(*cc.member(*out, p)));
-            outs.back()->slots = N;
-        }
-    }
-    if (want_count) {
-        fold(cnt);
-        outs.push_back(cnt);
-        outs.back()->slots = N;
-    }
-    return outs;
+    op.count = [&](Engine &E, CtPtr &A, int, CtPtr &cnt) { addMembers(E, cnt, *E.mul_const(*A, scale_down)); };
+    // the stacked column product with nothing added to the indicator: mul(A_z, column)'s words
+    op.product = [](Engine &E, const Ciphertext &A, int, const Ciphertext &stack, int Pg) {
+        return E.mul_pairs_const(A, 0.0, stack, Pg);
+    };
+    return allPairs(op);
 }
 
 LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int ps_split) {
@@ -2581,12 +2312,12 @@ LexRankLevels lexRankLevels(int key_level, int nkeys, int n, int dg, int df, int
 // of 1/2 of the L indicators are postponed to the closing 2^-L.
 CtPtr DirectSortN::lexRank(const std::vector<const Ciphertext *> &keys, double eps, SignFunc f,
                            const SignConfig &cfg) {
-    const SortShape s = rankShape(N, max_batch);
+    const std::string me = "lex rank";
     const int L = (int)keys.size();
-    if (L < 2 || L > 4) throw std::invalid_argument("lex rank: 2 to 4 keys, got " + std::to_string(L));
-    if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("lex rank: eps must lie in (0, 0.5)");
+    if (L < 2 || L > 4) throw std::invalid_argument(me + ": nkeys must lie in 2..4, got " + std::to_string(L));
+    checkEps(me, eps);
     for (int l = 0; l < L; ++l) {
-        const std::string which = "lex rank: key " + std::to_string(l);
+        const std::string which = me + ": key " + std::to_string(l);
         if (!keys[l]) throw std::invalid_argument(which + " is null");
         if (keys[l]->batch != 1) throw std::invalid_argument(which + " is a stack");
         if (keys[l]->slots != keys[0]->slots)
@@ -2598,85 +2329,44 @@ CtPtr DirectSortN::lexRank(const std::vector<const Ciphertext *> &keys, double e
     }
     const LexRankLevels lv =
         lexRankLevels(keys[0]->level, L, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    if (lv.rank_level > cc.params().L)
-        throw std::runtime_error("lex rank: " + std::to_string(L) + " keys at level " + std::to_string(keys[0]->level) +
-                                 " need " + std::to_string(lv.rank_level) + " levels, the context has " +
-                                 std::to_string(cc.params().L) + ": no levels left");
+    checkDepth(me, std::to_string(L) + " keys at level " + std::to_string(keys[0]->level), lv.rank_level, cc.params().L);
     if (!cache_masks) refresh_masks();
-    std::optional<AlgoPhase> ph;
-    ph.emplace("lex_baby");
-    std::vector<std::vector<CtPtr>> baby(L);
-    std::vector<CtPtr> dups(L);
-    for (int l = 0; l < L; ++l) {
-        baby[l] = babySteps(*keys[l], s.np);
-        for (auto &b : baby[l]) b->slots = s.num_slots;
-        dups[l] = cc.clone(*keys[l]);
-        dups[l]->slots = s.num_slots;
-    }
-    ph.reset();
-    std::vector<int> mine(s.num_batch);
-    for (int b = 0; b < s.num_batch; ++b) mine[b] = b;
-    // the last key's tie-break offsets, at the level the differences sit at
-    std::map<int, PtPtr> offs;
-    if (tiebreak > 0.0) offs = tiebreakOffsets(s.num_slots, mine, baby[0][0]->level + 1, tiebreak);
-    cc.sync();  // the baby steps, the dups and the offsets are read by every lane
+    PairOp op{"lex_baby", "lex_batches", "lex_fold"};
+    op.left = op.right = keys;
     // a chunk's sign runs over (2 L - 1) members per batch: the plain rank's footprint
-    const size_t chunk = (size_t)std::max(1, std::max(1, max_stack) / (2 * L - 1));
-    std::vector<const Ciphertext *> dp;
-    for (auto &d : dups) dp.push_back(d.get());
-    auto parts = run_lanes(mine, [&](Lane Ln, const std::vector<int> &bs) -> CtPtr {
-        Engine &E = *Ln.eng;
-        AlgoPhase lane_ph("lex_batches");
-        CtPtr acc;
-        for (size_t c0 = 0; c0 < bs.size(); c0 += chunk) {
-            std::vector<int> iss(bs.begin() + c0, bs.begin() + std::min(bs.size(), c0 + chunk));
-            const int B = (int)iss.size();
-            CtPtr sg;
-            {
-                std::vector<CtPtr> shifted;  // key-major
-                for (int l = 0; l < L; ++l)
-                    for (auto &x : vecRotsOptMany(Ln, baby[l], s.num_partition, s.num_slots, s.np, iss))
-                        shifted.push_back(x);
-                std::vector<const Ciphertext *> ptrs;
-                for (auto &x : shifted) ptrs.push_back(x.get());
-                std::vector<const Plaintext *> es;
-                if (tiebreak > 0.0)
-                    for (int b : iss) es.push_back(offs.at(b).get());
-                CtPtr d = E.sub_lex_stacked(dp, ptrs, es, eps);
-                shifted.clear();
-                sg = sign(*d, E, f, cfg);
-            }
-            if (sg->level != lv.sign_level) throw std::logic_error("lex rank: unexpected sign output level");
-            auto view = [&](int first) {  // B members of the sign's stack from member `first` on
-                Ciphertext v = *sg;
-                v.batch = B;
-                v.data = sg->data + (size_t)first * 2 * sg->limbs * E.n();
-                return v;
-            };
-            // Horner, innermost key first: T = (u_l - w_l) (T [+ 1]) + 2^(L-1-l) (w_l + 1)
-            CtPtr T;
-            for (int l = L - 2; l >= 0; --l) {
-                const Ciphertext u = view(2 * l * B), w = view((2 * l + 1) * B);
-                CtPtr prod = l == L - 2 ? E.mul_lex(view(2 * (L - 1) * B), 1.0, u, w) : E.mul_lex(*T, 0.0, u, w);
-                CtPtr sm = E.mul_const_to(*E.add_const(w, 1.0), (double)(1 << (L - 1 - l)), prod->level);
-                T = E.add(*prod, *sm);
-            }
-            E.add_inplace(acc, B == 1 ? *T : *E.sum_members(*T));
+    op.sign_members = 2 * L - 1;
+    op.want_count = true;
+    // the last key's tie-break offsets, at the level the differences sit at
+    op.offs_eps = tiebreak;
+    op.offs_level = lv.diff_level;
+    op.indicator = [&](Engine &E, PairChunk &ck) {
+        const int B = ck.B;
+        std::vector<const Ciphertext *> ptrs;
+        for (auto &x : ck.shifted) ptrs.push_back(x.get());
+        CtPtr d = E.sub_lex_stacked(ck.dups, ptrs, ck.offsets, eps);
+        ck.shifted.clear();
+        CtPtr sg = sign(*d, E, f, cfg);
+        d.reset();
+        if (sg->level != lv.sign_level) throw std::logic_error("lex rank: unexpected sign output level");
+        auto view = [&](int first) { return membersOf(E, *sg, first, B); };
+        // Horner, innermost key first: T = (u_l - w_l) (T [+ 1]) + 2^(L-1-l) (w_l + 1)
+        CtPtr T;
+        for (int l = L - 2; l >= 0; --l) {
+            const Ciphertext u = view(2 * l * B), w = view((2 * l + 1) * B);
+            CtPtr prod = l == L - 2 ? E.mul_lex(view(2 * (L - 1) * B), 1.0, u, w) : E.mul_lex(*T, 0.0, u, w);
+            CtPtr sm = E.mul_const_to(*E.add_const(w, 1.0), (double)(1 << (L - 1 - l)), prod->level);
+            T = E.add(*prod, *sm);
         }
-        return acc;
-    });
-    CtPtr rank;
-    for (auto &p : parts)
-        if (p) cc.add_inplace(rank, *p);
-    cc.sync();  // lane buffers return to their pools only after the main stream read them
-    parts.clear();
-    ph.emplace("lex_fold");
-    for (int i = 1; i < std::log2((double)s.num_partition) + 1; ++i)
-        rank = cc.add(*rank, *rot.rotate(*rank, s.num_slots / (1 << i)));
-    rank = cc.mul_const(*rank, 1.0 / (double)(1 << L));
-    // the self comparison: 1/2 at sign(0) on the last key, a clean 1 with the tie-break offset
-    cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5);
-    rank->slots = N;
+        return T;
+    };
+    op.count = [](Engine &E, CtPtr &T, int, CtPtr &acc) { addMembers(E, acc, *T); };
+    // the L indicators' postponed factors of 1/2, then the self comparison: 1/2 at
+    // sign(0) on the last key, a clean 1 with the tie-break offset
+    op.closing = [&](CtPtr &rank) {
+        rank = cc.mul_const(*rank, 1.0 / (double)(1 << L));
+        cc.add_const_inplace(rank, tiebreak > 0.0 ? -1.0 : -0.5);
+    };
+    CtPtr rank = allPairs(op)[0];
     if (rank->level != lv.rank_level) throw std::logic_error("lex rank: unexpected output level");
     return rank;
 }

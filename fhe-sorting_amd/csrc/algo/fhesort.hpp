@@ -475,8 +475,60 @@ class DirectSortN {
         RotationComposerN *rot;
     };
     Lane lane(int l);
+    // one result of work(lane, its batches) per lane, in lane order
     template <class F>
-    std::vector<CtPtr> run_lanes(const std::vector<int> &batches, F &&work);
+    auto run_lanes(const std::vector<int> &batches, F &&work);
+    // One chunk of comparator batches inside a lane, as allPairs hands it to an
+    // operator's indicator: the left operands' copies at num_slots, the right
+    // operands shifted by every batch of the chunk (operand-major, B each; the
+    // callback clears them once its differences are enqueued) and, where the
+    // operator asked for them, the chunk's tie-break offsets.
+    struct PairChunk {
+        int B;
+        const std::vector<const Ciphertext *> &dups;
+        std::vector<CtPtr> &shifted;
+        std::vector<const Plaintext *> offsets;
+    };
+    // What an operator hands allPairs: its operands, its sizes
+    // and the three places where its predicate and its product differ.
+    struct PairOp {
+        const char *baby_phase, *batch_phase, *fold_phase;
+        std::vector<const Ciphertext *> left, right;
+        std::vector<const Ciphertext *> cols;  // empty: the column-free form (a rank)
+        double col_scale = 1.0;                // every column enters as mul_const_to(col, col_scale, col_level)
+        int col_level = 0;
+        int sign_members = 1;  // members of a chunk's sign / series stack per batch: bounds the chunk
+        int ind_members = 1;   // indicator members per batch that meet the columns: bounds the column groups
+        bool want_count = false;
+        bool sharded = false;   // constructRank alone: this rank's batches, then reducePartial
+        double offs_eps = 0.0;  // > 0: the tie-break offsets E_b of this eps at offs_level
+        int offs_level = 0;
+        // the chunk's indicator stack (level asserted by the operator)
+        std::function<CtPtr(Engine &, PairChunk &)> indicator;
+        // adds the chunk's contribution to the lane's count / present partial
+        // (the column-free form may consume the indicator in place)
+        std::function<void(Engine &, CtPtr &ind, int B, CtPtr &cnt)> count;
+        // indicator x the chunk's shifted columns (column-major, Pg columns of B)
+        std::function<CtPtr(Engine &, const Ciphertext &ind, int B, const Ciphertext &cols, int Pg)> product;
+        // on the folded count, inside the fold phase (a closing constant)
+        std::function<void(CtPtr &cnt)> closing;
+    };
+    // The all-pairs layout every operator of DESIGN.md §6 walks: baby steps,
+    // chunks of batches on the lanes, the lanes' partials added on the main
+    // stream, the fold over the partitions.  Returns cols.size() * ind_members
+    // sums, then (want_count) ind_members counts, each of N slots.
+    std::vector<CtPtr> allPairs(const PairOp &op);
+    // add(v, rotate(v, num_slots / 2^i)) over the partitions: the rank's fold
+    void foldPartitions(CtPtr &v, const SortShape &s);
+    // the members of a folded stack as single ciphertexts of N slots
+    std::vector<CtPtr> splitMembers(const CtPtr &v, int members);
+    // columns per stacked product: the member bound over the largest chunk a lane stacks
+    int perProduct(size_t batches, size_t chunk, int ind_members) const;
+    // the lane partial of column groups, in column order
+    static CtPtr stackGroups(Engine &E, const std::vector<CtPtr> &accs);
+    // null, stack, slot count (slots >= 0: against `noun`, "the keys") and depth of every column
+    static void checkColumns(const std::string &op, const std::string &noun,
+                             const std::vector<const Ciphertext *> &cols, int slots, int max_level);
     CtPtr vecRotsOpt(Lane L, const std::vector<CtPtr> &baby, int num_partition, int num_slots, int np, int is);
     // vecRotsOpt of several batches: the giant-step rotations of all of them
     // (one amount per batch) run in shared launches (RotationComposerN::rotateMembers)

@@ -91,6 +91,33 @@ SignConfig cfgof(int n, int dg, int df) { return SignConfig(CompositeSignConfig(
     do {                                                          \
         if (!(x)) throw std::invalid_argument("null argument: " #x); \
     } while (0)
+
+// The context's sorter for (N, rotation set), made on first use, with the
+// context's settings copied into it and the unsharded defaults; a call site
+// that shards sets the shard fields afterwards.
+DirectSortN &sorter_for(fhe_ctx *ctx, int N, const int32_t *rots, int nrot) {
+    auto key = std::make_pair(N, std::vector<int>(rots, rots + nrot));
+    auto &slot = ctx->sorters[key];
+    if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, key.second);
+    DirectSortN &ds = *slot;
+    ds.max_stack = ctx->sort_stack;
+    ds.lanes = ctx->sort_lanes;
+    ds.max_col_members = ctx->sort_col_members;
+    ds.cache_masks = ctx->mask_cache;
+    ds.tiebreak = ctx->sort_tiebreak;
+    ds.shard_rank = 0;
+    ds.shard_world = 1;
+    ds.allreduce = nullptr;
+    return ds;
+}
+// the ciphertexts behind `count` handles; a null handle gives a null entry,
+// which the operator refuses by its index
+std::vector<const Ciphertext *> raw(const fhe_ct *const *hs, int count) {
+    std::vector<const Ciphertext *> v;
+    for (int i = 0; i < count; ++i) v.push_back(hs[i] ? hs[i]->p.get() : nullptr);
+    return v;
+}
+const Ciphertext *raw(const fhe_ct *h) { return h ? h->p.get() : nullptr; }
 }  // namespace
 
 extern "C" {
@@ -592,14 +619,7 @@ int fhe_direct_sort(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
         NEED(ctx);
         NEED(x);
         CtAllReduce reduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);  // validates the shard first
-        auto key = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[key];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, key.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.cache_masks = ctx->mask_cache;
-        ds.tiebreak = ctx->sort_tiebreak;
+        DirectSortN &ds = sorter_for(ctx, N, rots, nrot);
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
         ds.allreduce = std::move(reduce);
@@ -622,32 +642,14 @@ int fhe_direct_sort_columns(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank,
         NEED(outs);
         if (!key && !rank) throw std::invalid_argument("fhe_direct_sort_columns: neither a key nor a rank given");
         if (ncols < 1 || !cols) throw std::invalid_argument("fhe_direct_sort_columns: ncols must be >= 1");
-        const Ciphertext &packing = rank ? *rank->p : *key->p;
-        std::vector<const Ciphertext *> v;
-        for (int p = 0; p < ncols; ++p) {
-            const std::string which = "fhe_direct_sort_columns: column " + std::to_string(p);
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
-            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (cols[p]->p->slots != packing.slots)
-                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the " +
-                                            (rank ? "rank " : "key ") + std::to_string(packing.slots));
-            v.push_back(cols[p]->p.get());
-        }
+        const std::vector<const Ciphertext *> v = raw(cols, ncols);
         CtAllReduce reduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.tiebreak = ctx->sort_tiebreak;
+        DirectSortN &ds = sorter_for(ctx, N, rots, nrot);
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
         ds.allreduce = std::move(reduce);
-        // the depth refusal (a column below the series output) is raised by the
-        // index check before it starts any work
+        // the columns' refusals (null, stack, slot count, a column below the series
+        // output) are raised by the operator before it starts any work on them
         std::vector<CtPtr> r = rank ? ds.rotationIndexCheckColumns(*rank->p, v)
                                     : ds.sortColumns(*key->p, v, SignFunc::CompositeSign, cfgof(n, dg, df));
         for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
@@ -688,38 +690,12 @@ int fhe_direct_select(fhe_ctx *ctx, const fhe_ct *key, const fhe_ct *rank, const
         NEED(outs);
         if (!key && !rank) throw std::invalid_argument("fhe_direct_select: neither a key nor a rank given");
         if (ncols < 1 || !cols) throw std::invalid_argument("fhe_direct_select: ncols must be >= 1");
-        const Ciphertext &packing = rank ? *rank->p : *key->p;
-        std::vector<const Ciphertext *> v;
-        for (int p = 0; p < ncols; ++p) {
-            const std::string which = "fhe_direct_select: column " + std::to_string(p);
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
-            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (cols[p]->p->slots != packing.slots)
-                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the " +
-                                            (rank ? "rank " : "key ") + std::to_string(packing.slots));
-            v.push_back(cols[p]->p.get());
-        }
-        if (ntargets < 1 || ntargets > N || !targets)
-            throw std::invalid_argument("fhe_direct_select: ntargets must lie in 1.." + std::to_string(N));
-        for (int p = 0; p < ntargets; ++p)
-            if (targets[p] < 0 || targets[p] >= N)
-                throw std::invalid_argument("fhe_direct_select: target " + std::to_string(p) + " (" +
-                                            std::to_string(targets[p]) + ") is outside [0, " + std::to_string(N) + ")");
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.tiebreak = ctx->sort_tiebreak;
-        ds.shard_rank = 0;  // selection is unsharded; a sharded caller passes the reduced rank in
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
+        if (ntargets < 1 || !targets) throw std::invalid_argument("fhe_direct_select: ntargets must be >= 1");
+        const std::vector<const Ciphertext *> v = raw(cols, ncols);
         const std::vector<int> t(targets, targets + ntargets);
-        // the depth refusal (a column below the series output) is raised by the
-        // select before it starts any work on the columns
+        // selection is unsharded (a sharded caller passes the reduced rank in); the
+        // refusals of targets and columns are raised by the select before any work
+        DirectSortN &ds = sorter_for(ctx, N, rots, nrot);
         std::vector<CtPtr> r = rank ? ds.selectColumns(*rank->p, v, t)
                                     : ds.selectColumns(*key->p, v, t, SignFunc::CompositeSign, cfgof(n, dg, df));
         for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
@@ -748,44 +724,12 @@ int fhe_direct_group_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *rig
         if (!left_key || !left_key->p) throw std::invalid_argument("fhe_direct_group_sum: the left key is null");
         if (!right_key || !right_key->p) throw std::invalid_argument("fhe_direct_group_sum: the right key is null");
         if (ncols < 0) throw std::invalid_argument("fhe_direct_group_sum: ncols must be >= 0");
-        if (ncols == 0 && !count_out)
-            throw std::invalid_argument("fhe_direct_group_sum: neither a column nor the count is asked for");
         if (ncols > 0 && (!cols || !outs)) throw std::invalid_argument("fhe_direct_group_sum: null column or output array");
-        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_group_sum: eps must lie in (0, 0.5)");
-        const Ciphertext &kl = *left_key->p, &kr = *right_key->p;
-        if (kl.batch != 1) throw std::invalid_argument("fhe_direct_group_sum: the left key is a stack");
-        if (kr.batch != 1) throw std::invalid_argument("fhe_direct_group_sum: the right key is a stack");
-        if (kr.slots != kl.slots)
-            throw std::invalid_argument("fhe_direct_group_sum: the right key has " + std::to_string(kr.slots) +
-                                        " slots, the left key " + std::to_string(kl.slots));
-        if (kr.level != kl.level)
-            throw std::invalid_argument("fhe_direct_group_sum: the keys sit at different levels (" +
-                                        std::to_string(kl.level) + ", " + std::to_string(kr.level) + ")");
-        std::vector<const Ciphertext *> v;
-        for (int p = 0; p < ncols; ++p) {
-            const std::string which = "fhe_direct_group_sum: column " + std::to_string(p);
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
-            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (cols[p]->p->slots != kl.slots)
-                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the keys " +
-                                            std::to_string(kl.slots));
-            v.push_back(cols[p]->p.get());
-        }
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.shard_rank = 0;  // unsharded, like the select
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
-        // the depth refusals (a column too deep, a context too shallow) are raised
-        // by the operator before it starts any work
-        std::vector<CtPtr> r =
-            ds.groupSums(kl, kr, v, eps, count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        // every refusal about the operands (shapes, eps, a column too deep, a context
+        // too shallow) is raised by the operator before it starts any work; unsharded
+        std::vector<CtPtr> r = sorter_for(ctx, N, rots, nrot)
+                                   .groupSums(*left_key->p, *right_key->p, raw(cols, ncols), eps, count_out != nullptr,
+                                              SignFunc::CompositeSign, cfgof(n, dg, df));
         for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
         if (count_out) *count_out = wrap(r[(size_t)ncols]);
     });
@@ -810,47 +754,13 @@ int fhe_direct_gather(fhe_ctx *ctx, const fhe_ct *pos_l, const fhe_ct *pos_r, co
         if (!pos_r || !pos_r->p) throw std::invalid_argument("fhe_direct_gather: the right position is null");
         if (ncols < 0) throw std::invalid_argument("fhe_direct_gather: ncols must be >= 0");
         if (noffsets < 1 || !offsets) throw std::invalid_argument("fhe_direct_gather: noffsets must be >= 1");
-        if (ncols == 0 && !want_present)
-            throw std::invalid_argument("fhe_direct_gather: neither a column nor the present flag is asked for");
         if (!outs || (ncols > 0 && !cols)) throw std::invalid_argument("fhe_direct_gather: null column or output array");
-        for (int k = 0; k < noffsets; ++k)
-            if (offsets[k] < -(N - 1) || offsets[k] > N - 1)
-                throw std::invalid_argument("fhe_direct_gather: offset " + std::to_string(k) + " (" +
-                                            std::to_string(offsets[k]) + ") is outside [-(N - 1), N - 1]");
-        const Ciphertext &pl = *pos_l->p, &pr = *pos_r->p;
-        if (pl.batch != 1) throw std::invalid_argument("fhe_direct_gather: the left position is a stack");
-        if (pr.batch != 1) throw std::invalid_argument("fhe_direct_gather: the right position is a stack");
-        if (pr.slots != pl.slots)
-            throw std::invalid_argument("fhe_direct_gather: the right position has " + std::to_string(pr.slots) +
-                                        " slots, the left position " + std::to_string(pl.slots));
-        if (pr.level != pl.level)
-            throw std::invalid_argument("fhe_direct_gather: the positions sit at different levels (" +
-                                        std::to_string(pl.level) + ", " + std::to_string(pr.level) + ")");
-        std::vector<const Ciphertext *> v;
-        for (int p = 0; p < ncols; ++p) {
-            const std::string which = "fhe_direct_gather: column " + std::to_string(p);
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
-            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (cols[p]->p->slots != pl.slots)
-                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) +
-                                            " slots, the positions " + std::to_string(pl.slots));
-            v.push_back(cols[p]->p.get());
-        }
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.shard_rank = 0;  // unsharded, like the select
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
-        // the depth refusals (a column too deep, a context too shallow) are raised
-        // by the operator before it starts any work
-        std::vector<CtPtr> r = ds.gatherColumns(pl, pr, v, std::vector<int>(offsets, offsets + noffsets),
-                                                want_present != 0, sum_offsets != 0);
+        // every refusal about the operands (shapes, offsets, a column too deep, a context
+        // too shallow) is raised by the operator before it starts any work; unsharded
+        std::vector<CtPtr> r = sorter_for(ctx, N, rots, nrot)
+                                   .gatherColumns(*pos_l->p, *pos_r->p, raw(cols, ncols),
+                                                  std::vector<int>(offsets, offsets + noffsets), want_present != 0,
+                                                  sum_offsets != 0);
         if ((long long)r.size() != nout) throw std::logic_error("fhe_direct_gather: unexpected output count");
         for (size_t i = 0; i < r.size(); ++i) outs[i] = wrap(r[i]);
     });
@@ -929,62 +839,14 @@ int fhe_direct_running_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *l
         NEED(ctx);
         if (!left_key || !left_key->p) throw std::invalid_argument("fhe_direct_running_sum: the left key is null");
         if (!right_key || !right_key->p) throw std::invalid_argument("fhe_direct_running_sum: the right key is null");
-        if (mode < FHE_RUN_ROWS || mode > FHE_RUN_BETWEEN)
-            throw std::invalid_argument("fhe_direct_running_sum: mode must lie in 0..3, got " + std::to_string(mode));
-        if (mode == FHE_RUN_BETWEEN && (!left_lo || !left_lo->p))
-            throw std::invalid_argument("fhe_direct_running_sum: FHE_RUN_BETWEEN needs left_lo, the lower bound");
-        if (mode != FHE_RUN_BETWEEN && left_lo)
-            throw std::invalid_argument("fhe_direct_running_sum: left_lo is given outside FHE_RUN_BETWEEN");
         if (ncols < 0) throw std::invalid_argument("fhe_direct_running_sum: ncols must be >= 0");
-        if (ncols == 0 && !count_out)
-            throw std::invalid_argument("fhe_direct_running_sum: neither a column nor the count is asked for");
         if (ncols > 0 && (!cols || !outs))
             throw std::invalid_argument("fhe_direct_running_sum: null column or output array");
-        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_running_sum: eps must lie in (0, 0.5)");
-        const Ciphertext &kl = *left_key->p, &kr = *right_key->p;
-        if (kl.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: the left key is a stack");
-        if (kr.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: the right key is a stack");
-        if (kr.slots != kl.slots)
-            throw std::invalid_argument("fhe_direct_running_sum: the right key has " + std::to_string(kr.slots) +
-                                        " slots, the left key " + std::to_string(kl.slots));
-        if (kr.level != kl.level)
-            throw std::invalid_argument("fhe_direct_running_sum: the keys sit at different levels (" +
-                                        std::to_string(kl.level) + ", " + std::to_string(kr.level) + ")");
-        if (left_lo) {
-            const Ciphertext &lo = *left_lo->p;
-            if (lo.batch != 1) throw std::invalid_argument("fhe_direct_running_sum: left_lo is a stack");
-            if (lo.slots != kl.slots)
-                throw std::invalid_argument("fhe_direct_running_sum: left_lo has " + std::to_string(lo.slots) +
-                                            " slots, the left key " + std::to_string(kl.slots));
-            if (lo.level != kl.level)
-                throw std::invalid_argument("fhe_direct_running_sum: left_lo sits at level " + std::to_string(lo.level) +
-                                            ", the left key at " + std::to_string(kl.level));
-        }
-        std::vector<const Ciphertext *> v;
-        for (int p = 0; p < ncols; ++p) {
-            const std::string which = "fhe_direct_running_sum: column " + std::to_string(p);
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(which + " is null");
-            if (cols[p]->p->batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (cols[p]->p->slots != kl.slots)
-                throw std::invalid_argument(which + " has " + std::to_string(cols[p]->p->slots) + " slots, the keys " +
-                                            std::to_string(kl.slots));
-            v.push_back(cols[p]->p.get());
-        }
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.shard_rank = 0;  // unsharded, like the group sums
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
-        // the depth refusals (a column too deep, a context too shallow) are raised
-        // by the operator before it starts any work
-        std::vector<CtPtr> r = ds.runningSums(kl, left_lo ? left_lo->p.get() : nullptr, kr, v, mode, eps,
-                                              count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        // every refusal about the operands (the mode and its lower bound, shapes, eps, a column too deep,
+        // a context too shallow) is raised by the operator before it starts any work; unsharded
+        std::vector<CtPtr> r = sorter_for(ctx, N, rots, nrot)
+                                   .runningSums(*left_key->p, raw(left_lo), *right_key->p, raw(cols, ncols), mode, eps,
+                                                count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
         for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
         if (count_out) *count_out = wrap(r[(size_t)ncols]);
     });
@@ -1042,56 +904,17 @@ int fhe_direct_window_sum(fhe_ctx *ctx, const fhe_ct *const *part_left, const fh
     return guard([&] {
         NEED(ctx);
         const std::string me = "fhe_direct_window_sum: ";
-        if (mode < FHE_WIN_ROWS || mode > FHE_WIN_GROUP)
-            throw std::invalid_argument(me + "mode must lie in 0..4, got " + std::to_string(mode));
-        if (nparts < 1 || nparts > 3)
+        if (nparts < 0 || nparts > 3)  // the arrays are read up to nparts
             throw std::invalid_argument(me + "nparts must lie in 1..3, got " + std::to_string(nparts));
-        const int F = nparts + (mode != FHE_WIN_GROUP ? 1 : 0);
-        if (F < 2) throw std::invalid_argument(me + "one partition key under FHE_WIN_GROUP is fhe_direct_group_sum");
-        if (F > 4) throw std::invalid_argument(me + "at most 4 factors, got " + std::to_string(F));
         if (!part_left || !part_right) throw std::invalid_argument(me + "null partition key array");
-        if (mode == FHE_WIN_GROUP && (order_left || order_right || order_lo))
-            throw std::invalid_argument(me + "an order key is given under FHE_WIN_GROUP");
-        if (mode != FHE_WIN_GROUP && (!order_left || !order_left->p || !order_right || !order_right->p))
-            throw std::invalid_argument(me + "the mode needs order_left and order_right");
-        if (mode == FHE_WIN_BETWEEN && (!order_lo || !order_lo->p))
-            throw std::invalid_argument(me + "FHE_WIN_BETWEEN needs order_lo, the lower bound");
-        if (mode != FHE_WIN_BETWEEN && order_lo)
-            throw std::invalid_argument(me + "order_lo is given outside FHE_WIN_BETWEEN");
         if (ncols < 0) throw std::invalid_argument(me + "ncols must be >= 0");
-        if (ncols == 0 && !count_out) throw std::invalid_argument(me + "neither a column nor the count is asked for");
         if (ncols > 0 && (!cols || !outs)) throw std::invalid_argument(me + "null column or output array");
-        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument(me + "eps must lie in (0, 0.5)");
-        std::vector<const Ciphertext *> pl, pr, v;
-        for (int g = 0; g < nparts; ++g) {
-            if (!part_left[g] || !part_left[g]->p)
-                throw std::invalid_argument(me + "left partition key " + std::to_string(g) + " is null");
-            if (!part_right[g] || !part_right[g]->p)
-                throw std::invalid_argument(me + "right partition key " + std::to_string(g) + " is null");
-            pl.push_back(part_left[g]->p.get());
-            pr.push_back(part_right[g]->p.get());
-        }
-        for (int p = 0; p < ncols; ++p) {
-            if (!cols[p] || !cols[p]->p) throw std::invalid_argument(me + "column " + std::to_string(p) + " is null");
-            v.push_back(cols[p]->p.get());
-        }
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.max_col_members = ctx->sort_col_members;
-        ds.cache_masks = ctx->mask_cache;
-        ds.shard_rank = 0;  // unsharded, like the running sums
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
-        // the shape refusals (stacks, slot counts, levels) and the depth refusals (a column
-        // too deep, a context too shallow) are raised by the operator before it starts any work
-        std::vector<CtPtr> r = ds.windowSums(pl, pr, order_left ? order_left->p.get() : nullptr,
-                                             order_lo ? order_lo->p.get() : nullptr,
-                                             order_right ? order_right->p.get() : nullptr, v, mode, eps,
-                                             count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
+        // every refusal about the operands (the mode and the keys that go with it, shapes, eps, a column
+        // too deep, a context too shallow) is raised by the operator before it starts any work; unsharded
+        std::vector<CtPtr> r = sorter_for(ctx, N, rots, nrot)
+                                   .windowSums(raw(part_left, nparts), raw(part_right, nparts), raw(order_left),
+                                               raw(order_lo), raw(order_right), raw(cols, ncols), mode, eps,
+                                               count_out != nullptr, SignFunc::CompositeSign, cfgof(n, dg, df));
         for (int p = 0; p < ncols; ++p) outs[p] = wrap(r[(size_t)p]);
         if (count_out) *count_out = wrap(r[(size_t)ncols]);
     });
@@ -1163,37 +986,13 @@ int fhe_direct_lex_rank(fhe_ctx *ctx, const fhe_ct *const *keys, int nkeys, doub
     return guard([&] {
         NEED(ctx);
         NEED(rank);
-        if (nkeys < 2 || nkeys > 4)
+        if (nkeys < 0 || nkeys > 4)  // the array is read up to nkeys
             throw std::invalid_argument("fhe_direct_lex_rank: nkeys must lie in 2..4, got " + std::to_string(nkeys));
         NEED(keys);
-        if (!(eps > 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_direct_lex_rank: eps must lie in (0, 0.5)");
-        std::vector<const Ciphertext *> v;
-        for (int l = 0; l < nkeys; ++l) {
-            const std::string which = "fhe_direct_lex_rank: key " + std::to_string(l);
-            if (!keys[l] || !keys[l]->p) throw std::invalid_argument(which + " is null");
-            const Ciphertext &k = *keys[l]->p;
-            if (k.batch != 1) throw std::invalid_argument(which + " is a stack");
-            if (!v.empty() && k.slots != v[0]->slots)
-                throw std::invalid_argument(which + " has " + std::to_string(k.slots) + " slots, key 0 " +
-                                            std::to_string(v[0]->slots));
-            if (!v.empty() && k.level != v[0]->level)
-                throw std::invalid_argument(which + " sits at level " + std::to_string(k.level) + ", key 0 at level " +
-                                            std::to_string(v[0]->level) + ": the keys' levels differ");
-            v.push_back(&k);
-        }
-        auto skey = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[skey];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, skey.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
-        ds.cache_masks = ctx->mask_cache;
-        ds.tiebreak = ctx->sort_tiebreak;
-        ds.shard_rank = 0;  // unsharded, like the select and the group sums
-        ds.shard_world = 1;
-        ds.allreduce = nullptr;
-        // the depth refusal (a context too shallow) is raised by the operator before it starts any work
-        *rank = wrap(ds.lexRank(v, eps, SignFunc::CompositeSign, cfgof(n, dg, df)));
+        // every refusal about the keys (their count, shapes, eps, a context too shallow) is
+        // raised by the operator before it starts any work; unsharded
+        *rank = wrap(sorter_for(ctx, N, rots, nrot)
+                         .lexRank(raw(keys, nkeys), eps, SignFunc::CompositeSign, cfgof(n, dg, df)));
     });
 }
 int fhe_lex_rank_levels(int key_level, int nkeys, int n, int dg, int df, int *rank_level) {
@@ -1280,16 +1079,11 @@ int fhe_sort_hybrid(fhe_ctx *ctx, const fhe_ct *x, const fhe_ct *rank, int N, co
         if (mask_mode < 0 || mask_mode > 3) throw std::invalid_argument("sort_hybrid: mask_mode must be 0..3");
         if (shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world)
             throw std::invalid_argument("sort_hybrid: bad shard");
-        auto key = std::make_pair(N, std::vector<int>(rots, rots + nrot));
-        auto &slot = ctx->sorters[key];
-        if (!slot) slot = std::make_unique<DirectSortN>(*ctx->eng, N, key.second);
-        DirectSortN &ds = *slot;
-        ds.max_stack = ctx->sort_stack;
-        ds.lanes = ctx->sort_lanes;
+        CtAllReduce reduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);
+        DirectSortN &ds = sorter_for(ctx, N, rots, nrot);
         ds.shard_rank = shard_rank;
         ds.shard_world = shard_world;
-        ds.allreduce = make_allreduce(ctx, shard_rank, shard_world, fn, user);
-        ds.tiebreak = ctx->sort_tiebreak;
+        ds.allreduce = std::move(reduce);
         ds.hybrid_max_array = max_array;
         ds.hybrid_mask = mask_mode;
         if (mode == 1) {

@@ -374,15 +374,9 @@ struct Engine::Impl {
     // pass fused with the key-switch inner product for the FP-class targets
     // (dev::ntt_row_ks; integer targets keep the row pass + ks_inner)
     bool ks_fuse(int members) const {
-        static const int on = [] {
-            const char *e = std::getenv("FHE_KS_FUSE");
-            return e ? std::atoi(e) : 1;
-        }();
+        static const bool on = env_switch("FHE_KS_FUSE", 1);
         // FHE_KS_FUSE_MIN (A/B): the fewest members a fused launch takes (default 4)
-        static const int min_members = [] {
-            const char *e = std::getenv("FHE_KS_FUSE_MIN");
-            return e ? std::max(1, std::atoi(e)) : 4;
-        }();
+        static const int min_members = std::max(1, env_switch("FHE_KS_FUSE_MIN", 4));
         return on && members >= min_members && (P.logN == 16 || P.logN == 17);
     }
     // FHE_KS_FUSE_INT (A/B, default 1; round 6, verdict r5 item 2): the integer-class
@@ -391,10 +385,7 @@ struct Engine::Impl {
     // (profiles/r6_ab/ks_fuse_int_ab.jsonl); round 5 had measured the fused integer
     // launch per target against the FP one, not against the row pass + ks_inner it replaces
     static bool ks_fuse_int() {
-        static const bool on = [] {
-            const char *e = std::getenv("FHE_KS_FUSE_INT");
-            return e ? std::atoi(e) != 0 : true;
-        }();
+        static const bool on = env_switch("FHE_KS_FUSE_INT", 1);
         return on;
     }
     // FHE_MULTAIL_OWN (A/B, default 1): a one-digit HMult (ell <= alpha; 124 of the
@@ -402,10 +393,7 @@ struct Engine::Impl {
     // limbs below ell - 1 to the closing row pass (k_ntt_fwd_row<5, ...>) instead of
     // storing it from k_ntt_row_ks and reading it back; 0: the accumulator path
     static bool multail_own() {
-        static const bool on = [] {
-            const char *e = std::getenv("FHE_MULTAIL_OWN");
-            return e ? std::atoi(e) != 0 : true;
-        }();
+        static const bool on = env_switch("FHE_MULTAIL_OWN", 1);
         return on;
     }
     // cols_only: the forward NTT's column pass alone (the row pass runs fused
@@ -796,6 +784,29 @@ CtPtr Engine::new_ct(int level, int slots, double scale, size_t limbs, int batch
     c->scale = scale;
     c->limbs = limbs;
     return c;
+}
+
+// The tail of a stacked product of `members` HMults at a's level: the refusals
+// mul raises, the three counters, d01 / d2, the caller's tensor(d01, d2) launch
+// into them (with its own count_bytes terms), then ModUp, the key switch and
+// the rescale into a stack of `members` one level down.
+template <class Tensor>
+CtPtr Engine::product_tail(const Ciphertext &a, int members, Tensor &&tensor) {
+    auto &I = *impl;
+    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
+    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
+    ctr.hmult += members;
+    ctr.keyswitch += members;
+    ctr.rescale += members;
+    const size_t nn = n(), ell = a.limbs;
+    auto d01m = I.alloc((size_t)members * 2 * ell * nn * 8), d2m = I.alloc((size_t)members * ell * nn * 8);
+    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
+    tensor(d01, d2);
+    const bool fuse = I.ks_fuse(members);
+    auto extm = I.modup(d2, ell, members, ell * nn, fuse);
+    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, members);
+    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, members, r->data, fuse);
+    return r;
 }
 
 // ================================================================ keys ====
@@ -1668,10 +1679,7 @@ CtPtr Engine::mul_plain_sum(const std::vector<const Ciphertext *> &a, const std:
 // FHE_RANK_STACK_MASKS (A/B, default 1): the masked sums of a chunk's batches in
 // one pass over the shared ciphertexts; 0: one mul_plain_sum per batch, stacked
 static bool stack_masks_enabled() {
-    static const bool on = [] {
-        const char *e = std::getenv("FHE_RANK_STACK_MASKS");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    static const bool on = env_switch("FHE_RANK_STACK_MASKS", 1);
     return on;
 }
 
@@ -1724,10 +1732,7 @@ CtPtr Engine::mul_plain_sum_batches(const std::vector<const Ciphertext *> &a,
 // FHE_SELECT_FUSED (A/B, default 1): mul_plain_sum_groups' sums of every group in
 // one pass over the shared plaintexts; 0: one mul_plain_sum per group, stacked
 static bool select_fused_enabled() {
-    static const bool on = [] {
-        const char *e = std::getenv("FHE_SELECT_FUSED");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    static const bool on = env_switch("FHE_SELECT_FUSED", 1);
     return on;
 }
 
@@ -1774,21 +1779,15 @@ CtPtr Engine::mul_plain_sum_groups(const Ciphertext &a, const std::vector<const 
 
 // FHE_TENSOR_LIN (A/B, default 1): mul_add's summands folded into the tensor pass
 static bool tensor_lin_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_TENSOR_LIN");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_TENSOR_LIN", 1);
+    return on;
 }
 
 // FHE_MUL_FOLD_CONST (A/B, default 1): mul_add's a_const added on load in the
 // tensor pass and its out_const there as a term of d0; 0: the separate
 // add_const / add_const_inplace launches.  Same words either way.
 static bool mul_fold_const() {
-    static const bool on = [] {
-        const char *e = std::getenv("FHE_MUL_FOLD_CONST");
-        return e ? std::atoi(e) != 0 : true;
-    }();
+    static const bool on = env_switch("FHE_MUL_FOLD_CONST", 1);
     return on;
 }
 
@@ -1922,15 +1921,11 @@ CtPtr Engine::square(const Ciphertext &a) { return mul(a, a); }
 
 // FHE_SORT_COLS_FUSED (A/B, default 1): mul_columns' tensor of every column in one pass
 static bool cols_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_SORT_COLS_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_SORT_COLS_FUSED", 1);
+    return on;
 }
 
 CtPtr Engine::mul_columns(const Ciphertext &a, const std::vector<const Ciphertext *> &cols) {
-    auto &I = *impl;
     if (cols.empty()) throw std::invalid_argument("mul_columns: no columns");
     for (size_t p = 0; p < cols.size(); ++p) {
         if (!cols[p]) throw std::invalid_argument("mul_columns: column " + std::to_string(p) + " is null");
@@ -1948,45 +1943,31 @@ CtPtr Engine::mul_columns(const Ciphertext &a, const std::vector<const Ciphertex
         }
         return prod.size() == 1 ? prod[0] : stack(v);
     }
-    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
-    std::vector<CtPtr> adj;  // the columns mul would level-adjust, kept until the tensor pass is enqueued
-    std::vector<const u64 *> cp;
-    for (auto *c : cols) {
-        if (c->level < a.level) {
-            adj.push_back(level_adjust(*c, a.level));
-            c = adj.back().get();
-        }
-        if (c->limbs != a.limbs) throw std::invalid_argument("mul_columns: limb count mismatch");
-        cp.push_back(c->data);
-    }
     const int B = a.batch, Pn = (int)cols.size(), PB = Pn * B;
-    ctr.hmult += PB;
-    ctr.keyswitch += PB;
-    ctr.rescale += PB;
     const size_t nn = n(), ell = a.limbs;
-    count_bytes(6.0 * ell + ks_units(ell), PB);
-    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    dev::ew_tensor_cols(d01, d2, a.data, cp.data(), Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
-    const bool fuse = I.ks_fuse(PB);
-    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
-    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
-    return r;
+    return product_tail(a, PB, [&](u64 *d01, u64 *d2) {
+        std::vector<CtPtr> adj;  // the columns mul would level-adjust, kept until the tensor pass is enqueued
+        std::vector<const u64 *> cp;
+        for (auto *c : cols) {
+            if (c->level < a.level) {
+                adj.push_back(level_adjust(*c, a.level));
+                c = adj.back().get();
+            }
+            if (c->limbs != a.limbs) throw std::invalid_argument("mul_columns: limb count mismatch");
+            cp.push_back(c->data);
+        }
+        count_bytes(6.0 * ell + ks_units(ell), PB);
+        dev::ew_tensor_cols(d01, d2, a.data, cp.data(), Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    });
 }
 
 // FHE_GROUP_FUSED (A/B, default 1): the one-pass kernels of mul_pairs and sub_pm_const_stacked
 static bool group_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_GROUP_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_GROUP_FUSED", 1);
+    return on;
 }
 
 CtPtr Engine::mul_pairs(const Ciphertext &a, const Ciphertext &a_add, const Ciphertext &b, int Pn) {
-    auto &I = *impl;
     if (Pn < 1) throw std::invalid_argument("mul_pairs: no columns");
     if (a.batch < 1 || a_add.batch != a.batch)
         throw std::invalid_argument("mul_pairs: a and a_add differ in member count");
@@ -2010,22 +1991,12 @@ CtPtr Engine::mul_pairs(const Ciphertext &a, const Ciphertext &a_add, const Ciph
         }
         return prod.size() == 1 ? prod[0] : stack(v);
     }
-    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
-    ctr.hmult += PB;
-    ctr.keyswitch += PB;
-    ctr.rescale += PB;
-    count_bytes(5.0 * ell + ks_units(ell), PB);
-    const int per = dev::tensor_pairs_per_thread();
-    count_bytes(4.0 * ell * ((Pn + per - 1) / per), B);
-    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    dev::ew_tensor_pairs(d01, d2, a.data, a_add.data, b.data, Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
-    const bool fuse = I.ks_fuse(PB);
-    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
-    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
-    return r;
+    return product_tail(a, PB, [&](u64 *d01, u64 *d2) {
+        count_bytes(5.0 * ell + ks_units(ell), PB);
+        const int per = dev::tensor_pairs_per_thread();
+        count_bytes(4.0 * ell * ((Pn + per - 1) / per), B);
+        dev::ew_tensor_pairs(d01, d2, a.data, a_add.data, b.data, Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    });
 }
 
 std::vector<CtPtr> Engine::rotate_hoisted(const Ciphertext &a, const std::vector<long> &ks) {
@@ -2573,11 +2544,8 @@ CtPtr Engine::sub_stacked(const Ciphertext &a0, const std::vector<const Cipherte
 }
 // FHE_TIEBREAK_FUSED (A/B, default 1): sub_add_plain_stacked's one-pass kernel
 static bool tiebreak_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_TIEBREAK_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_TIEBREAK_FUSED", 1);
+    return on;
 }
 CtPtr Engine::sub_add_plain_stacked(const Ciphertext &a0, const std::vector<const Ciphertext *> &bs,
                                     const std::vector<const Plaintext *> &ps) {
@@ -2669,11 +2637,8 @@ CtPtr Engine::sub_pm_const_stacked(const Ciphertext &a0, const std::vector<const
 }
 // FHE_GATHER_FUSED (A/B, default 1): the one-pass kernels of sub_offsets_stacked and mul_gather
 static bool gather_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_GATHER_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_GATHER_FUSED", 1);
+    return on;
 }
 CtPtr Engine::sub_offsets_stacked(const Ciphertext &a0, const std::vector<const Ciphertext *> &bs,
                                   const std::vector<int> &offsets) {
@@ -2735,7 +2700,6 @@ CtPtr Engine::sub_offsets_stacked(const Ciphertext &a0, const std::vector<const 
     return r;
 }
 CtPtr Engine::mul_gather(const Ciphertext &a, const Ciphertext &b, int Pn, int Kn) {
-    auto &I = *impl;
     if (Pn < 1) throw std::invalid_argument("mul_gather: no columns");
     if (Kn < 1) throw std::invalid_argument("mul_gather: no offsets");
     if (a.batch < 1 || a.batch % Kn != 0)
@@ -2762,30 +2726,17 @@ CtPtr Engine::mul_gather(const Ciphertext &a, const Ciphertext &b, int Pn, int K
             }
         return prod.size() == 1 ? prod[0] : stack(v);
     }
-    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
-    ctr.hmult += PKB;
-    ctr.keyswitch += PKB;
-    ctr.rescale += PKB;
-    count_bytes(5.0 * ell + ks_units(ell), PKB);
-    const int per = dev::tensor_gather_per_thread();
-    count_bytes(2.0 * ell * ((Kn + per - 1) / per), Pn * B);
-    auto d01m = I.alloc((size_t)PKB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PKB * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    dev::ew_tensor_gather(d01, d2, a.data, b.data, Pn, Kn, (int)ell, B, MODS, LOGN, ST);
-    const bool fuse = I.ks_fuse(PKB);
-    auto extm = I.modup(d2, ell, PKB, ell * nn, fuse);
-    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PKB);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PKB, r->data, fuse);
-    return r;
+    return product_tail(a, PKB, [&](u64 *d01, u64 *d2) {
+        count_bytes(5.0 * ell + ks_units(ell), PKB);
+        const int per = dev::tensor_gather_per_thread();
+        count_bytes(2.0 * ell * ((Kn + per - 1) / per), Pn * B);
+        dev::ew_tensor_gather(d01, d2, a.data, b.data, Pn, Kn, (int)ell, B, MODS, LOGN, ST);
+    });
 }
 // FHE_LEX_FUSED (A/B, default 1): the one-pass kernels of sub_lex_stacked and mul_lex
 static bool lex_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_LEX_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_LEX_FUSED", 1);
+    return on;
 }
 CtPtr Engine::sub_lex_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
                               const std::vector<const Plaintext *> &ps, double eps) {
@@ -2860,7 +2811,6 @@ CtPtr Engine::sub_lex_stacked(const std::vector<const Ciphertext *> &as, const s
     return r;
 }
 CtPtr Engine::mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, const Ciphertext &w) {
-    auto &I = *impl;
     if (u.batch < 1 || w.batch != u.batch || t.batch != u.batch)
         throw std::invalid_argument("mul_lex: t, u and w differ in member count");
     if (w.level != u.level || w.limbs != u.limbs) throw std::invalid_argument("mul_lex: u and w differ in level");
@@ -2868,32 +2818,19 @@ CtPtr Engine::mul_lex(const Ciphertext &t, double t_const, const Ciphertext &u, 
         return mul(t_const != 0.0 ? *add_const(t, t_const) : t, *sub(u, w));
     if (t.level != u.level || t.limbs != u.limbs)  // mul level-adjusts an operand: u - w first, then the product
         return mul_add(t, *sub(u, w), {}, {}, nullptr, nullptr, t_const, 0.0);
-    if (t.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
     const int B = t.batch;
-    ctr.hmult += B;
-    ctr.keyswitch += B;
-    ctr.rescale += B;
     const size_t nn = n(), ell = t.limbs;
-    // the product, the sub it replaces and, with a constant, add_const's copy
-    count_bytes(6.0 * ell + ks_units(ell) + 6.0 * ell + (t_const != 0.0 ? 4.0 * ell : 0.0), B);
-    auto d01m = I.alloc((size_t)B * 2 * ell * nn * 8), d2m = I.alloc((size_t)B * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    const host::SConst Ka = t_const != 0.0 ? host::const_at_scale(t_const, t.scale) : host::SConst{};
-    dev::ew_tensor_lex(d01, d2, t.data, u.data, w.data, (int)ell, B, 2 * ell * nn, Ka.k, Ka.sh, MODS, LOGN, ST);
-    const bool fuse = I.ks_fuse(B);
-    auto extm = I.modup(d2, ell, B, ell * nn, fuse);
-    auto r = new_ct(t.level + 1, t.slots, I.P.delta[t.level + 1], ell - 1, B);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
-    return r;
+    return product_tail(t, B, [&](u64 *d01, u64 *d2) {
+        // the product, the sub it replaces and, with a constant, add_const's copy
+        count_bytes(6.0 * ell + ks_units(ell) + 6.0 * ell + (t_const != 0.0 ? 4.0 * ell : 0.0), B);
+        const host::SConst Ka = t_const != 0.0 ? host::const_at_scale(t_const, t.scale) : host::SConst{};
+        dev::ew_tensor_lex(d01, d2, t.data, u.data, w.data, (int)ell, B, 2 * ell * nn, Ka.k, Ka.sh, MODS, LOGN, ST);
+    });
 }
 // FHE_RUN_FUSED (A/B, default 1): the one-pass kernels of sub_bounds_stacked and mul_pairs_const / mul_pairs_sub
 static bool run_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_RUN_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_RUN_FUSED", 1);
+    return on;
 }
 CtPtr Engine::sub_bounds_stacked(const std::vector<const Ciphertext *> &as, const std::vector<const Ciphertext *> &bs,
                                  const std::vector<double> &consts) {
@@ -2963,7 +2900,6 @@ CtPtr Engine::mul_pairs_sub(const Ciphertext &a, const Ciphertext &a_sub, const 
 }
 CtPtr Engine::mul_pairs_left(const char *what, const Ciphertext &a, const Ciphertext *w, double c, const Ciphertext &b,
                              int Pn) {
-    auto &I = *impl;
     const std::string me(what);
     if (Pn < 1) throw std::invalid_argument(me + ": no columns");
     if (a.batch < 1) throw std::invalid_argument(me + ": a holds no member");
@@ -2988,32 +2924,19 @@ CtPtr Engine::mul_pairs_left(const char *what, const Ciphertext &a, const Cipher
         }
         return prod.size() == 1 ? prod[0] : stack(v);
     }
-    if (a.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
-    ctr.hmult += PB;
-    ctr.keyswitch += PB;
-    ctr.rescale += PB;
-    count_bytes(5.0 * ell + ks_units(ell), PB);
-    const int per = dev::tensor_pairs_per_thread();
-    count_bytes((w ? 4.0 : 2.0) * ell * ((Pn + per - 1) / per), B);
-    auto d01m = I.alloc((size_t)PB * 2 * ell * nn * 8), d2m = I.alloc((size_t)PB * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    const host::SConst K = w ? host::SConst{} : host::const_at_scale(c, a.scale);
-    dev::ew_tensor_run(d01, d2, a.data, w ? w->data : nullptr, b.data, Pn, (int)ell, B, 2 * ell * nn, K.k, K.sh, MODS,
-                       LOGN, ST);
-    const bool fuse = I.ks_fuse(PB);
-    auto extm = I.modup(d2, ell, PB, ell * nn, fuse);
-    auto r = new_ct(a.level + 1, a.slots, I.P.delta[a.level + 1], ell - 1, PB);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, PB, r->data, fuse);
-    return r;
+    return product_tail(a, PB, [&](u64 *d01, u64 *d2) {
+        count_bytes(5.0 * ell + ks_units(ell), PB);
+        const int per = dev::tensor_pairs_per_thread();
+        count_bytes((w ? 4.0 : 2.0) * ell * ((Pn + per - 1) / per), B);
+        const host::SConst K = w ? host::SConst{} : host::const_at_scale(c, a.scale);
+        dev::ew_tensor_run(d01, d2, a.data, w ? w->data : nullptr, b.data, Pn, (int)ell, B, 2 * ell * nn, K.k, K.sh,
+                           MODS, LOGN, ST);
+    });
 }
 // FHE_WIN_FUSED (A/B, default 1): the one-pass kernels of sub_window_stacked and mul_sub_sub
 static bool win_fused_enabled() {
-    static const int on = [] {
-        const char *e = std::getenv("FHE_WIN_FUSED");
-        return e ? std::atoi(e) : 1;
-    }();
-    return on != 0;
+    static const bool on = env_switch("FHE_WIN_FUSED", 1);
+    return on;
 }
 CtPtr Engine::sub_window_stacked(const std::vector<const Ciphertext *> &part_as,
                                  const std::vector<const Ciphertext *> &part_bs, const Ciphertext *order_a,
@@ -3116,29 +3039,18 @@ CtPtr Engine::sub_window_stacked(const std::vector<const Ciphertext *> &part_as,
     return r;
 }
 CtPtr Engine::mul_sub_sub(const Ciphertext &u, const Ciphertext &w, const Ciphertext &u2, const Ciphertext &w2) {
-    auto &I = *impl;
     if (u.batch < 1 || w.batch != u.batch || u2.batch != u.batch || w2.batch != u.batch)
         throw std::invalid_argument("mul_sub_sub: the operands differ in member count");
     if (w.level != u.level || w.limbs != u.limbs) throw std::invalid_argument("mul_sub_sub: u and w differ in level");
     if (w2.level != u2.level || w2.limbs != u2.limbs) throw std::invalid_argument("mul_sub_sub: u2 and w2 differ in level");
     // the plain form (A/B), and operands at two levels (mul level-adjusts one): every step an op of its own
     if (!win_fused_enabled() || u2.level != u.level || u2.limbs != u.limbs) return mul(*sub(u, w), *sub(u2, w2));
-    if (u.level >= I.P.L) throw std::runtime_error("mul: no levels left");
-    if (!I.ks->relin) throw std::runtime_error("mul: no relinearisation key");
     const int B = u.batch;
-    ctr.hmult += B;
-    ctr.keyswitch += B;
-    ctr.rescale += B;
     const size_t nn = n(), ell = u.limbs;
-    count_bytes(11.0 * ell + ks_units(ell), B);
-    auto d01m = I.alloc((size_t)B * 2 * ell * nn * 8), d2m = I.alloc((size_t)B * ell * nn * 8);
-    u64 *d01 = static_cast<u64 *>(d01m->p), *d2 = static_cast<u64 *>(d2m->p);
-    dev::ew_tensor_win(d01, d2, u.data, w.data, u2.data, w2.data, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
-    const bool fuse = I.ks_fuse(B);
-    auto extm = I.modup(d2, ell, B, ell * nn, fuse);
-    auto r = new_ct(u.level + 1, u.slots, I.P.delta[u.level + 1], ell - 1, B);
-    I.mul_tail(static_cast<u64 *>(extm->p), d01, d2, ell, B, r->data, fuse);
-    return r;
+    return product_tail(u, B, [&](u64 *d01, u64 *d2) {
+        count_bytes(11.0 * ell + ks_units(ell), B);
+        dev::ew_tensor_win(d01, d2, u.data, w.data, u2.data, w2.data, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
+    });
 }
 CtPtr Engine::sub_plain_stacked(const Ciphertext &a, const std::vector<const Plaintext *> &ps) {
     if (ps.empty()) throw std::invalid_argument("sub_plain_stacked: no plaintexts");

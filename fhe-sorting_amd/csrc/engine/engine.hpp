@@ -16,6 +16,7 @@
 #include <complex>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -30,6 +31,14 @@ using i64 = int64_t;
 using PublicSeed = std::array<uint8_t, 32>;  // public stream v1 (csrc/wire/wire.hpp)
 
 struct DevMem;  // pooled device allocation (engine.hip)
+
+// An A/B switch from the environment: the integer value of `name`, `dflt` when
+// it is unset.  Every call site keeps the result in a function-local static, so
+// a switch is read once per process.
+inline int env_switch(const char *name, int dflt) {
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
 
 // A ciphertext batch: `batch` independent ciphertexts at one level, stored
 // [batch][2][limbs][n].  Every op applies member-wise in the same launches, so
@@ -496,6 +505,9 @@ class Engine {
   private:
     std::shared_ptr<int> ps_split_ = std::make_shared<int>(PS_SPLIT_OPENFHE);
     CtPtr new_ct(int level, int slots, double scale, size_t limbs, int batch = 1);
+    // what the stacked products share behind their own tensor pass (engine.hip)
+    template <class Tensor>
+    CtPtr product_tail(const Ciphertext &a, int members, Tensor &&tensor);
     std::vector<CtPtr> linear_sums_run(const std::vector<const Ciphertext *> &xs, const int64_t *K, const uint8_t *sh,
                                        const int64_t *Kc, const uint8_t *shc, size_t G, int target, bool rescale,
                                        const char *who);
