@@ -1150,6 +1150,24 @@ SortShape rankShape(int N, int max_batch) {
     s.np = rank_np(N, s.num_partition);
     return s;
 }
+SortShape pairShape(int Nl, int Nr, int max_batch) {
+    auto pow2 = [](int v) { return v >= 2 && (v & (v - 1)) == 0; };
+    if (!pow2(Nl) || !pow2(Nr))
+        throw std::invalid_argument("pair tables: the row counts must be powers of two >= 2, got (" + std::to_string(Nl) +
+                                    ", " + std::to_string(Nr) + ")");
+    const int N = std::max(Nl, Nr), n = std::min(Nl, Nr);
+    SortShape s = rankShape(N, max_batch);  // refuses a ring too small for N as the square shape does
+    s.num_partition = std::min(s.num_partition, n);
+    s.num_batch = n / s.num_partition;
+    s.num_slots = N * s.num_partition;
+    s.np = rank_np(N, s.num_partition);
+    return s;
+}
+int pairFoldSteps(int Nl, int Nr) {
+    int k = 0;
+    while (((long long)Nl << k) < Nr) ++k;
+    return k;
+}
 SortShape checkShape(int N, int max_batch) {
     SortShape s = rankShape(N, max_batch);
     s.np = check_np(N);
@@ -1593,13 +1611,37 @@ void DirectSortN::foldPartitions(CtPtr &v, const SortShape &s) {
         v = cc.add(*v, *rot.rotate(*v, s.num_slots / (1 << i)));
 }
 
-std::vector<CtPtr> DirectSortN::splitMembers(const CtPtr &v, int members) {
+void DirectSortN::foldResidues(CtPtr &v, int Nl, int Nr) {
+    for (int k = 0; k < pairFoldSteps(Nl, Nr); ++k) v = cc.add(*v, *rot.rotate(*v, Nl << k));
+}
+
+std::vector<CtPtr> DirectSortN::splitMembers(const CtPtr &v, int members, int slots) {
     std::vector<CtPtr> outs(members);
     for (int m = 0; m < members; ++m) {
         outs[m] = members == 1 ? v : cc.clone(*cc.member(*v, m));
-        outs[m]->slots = N;
+        outs[m]->slots = slots ? slots : N;
     }
     return outs;
+}
+
+DirectSortN::PairTables DirectSortN::pairTables(const std::string &op, bool rows_mode) const {
+    if (pair_left == 0 && pair_right == 0) return PairTables{N, N, false};
+    const std::string pair = "(" + std::to_string(pair_left) + ", " + std::to_string(pair_right) + ")";
+    pairShape(pair_left, pair_right, max_batch);  // powers of two >= 2 that the ring holds
+    if (std::max(pair_left, pair_right) != N)
+        throw std::invalid_argument(op + ": N = " + std::to_string(N) + " is not the larger of the pair tables " + pair);
+    if (rows_mode && pair_left != pair_right)
+        throw std::invalid_argument(op + ": the rows mode orders ties by index, which tables of different sizes " + pair +
+                                    " do not share");
+    return PairTables{pair_left, pair_right, true};
+}
+
+void DirectSortN::checkTableSlots(const std::string &op, const std::string &arg, const Ciphertext &c, bool left,
+                                  const PairTables &t) {
+    if (!t.set || c.slots == (left ? t.nl : t.nr)) return;
+    throw std::invalid_argument(op + ": " + arg + " has " + std::to_string(c.slots) + " slots, the pair tables are (" +
+                                std::to_string(t.nl) + ", " + std::to_string(t.nr) + "): a " + (left ? "left" : "right") +
+                                " operand needs " + std::to_string(left ? t.nl : t.nr));
 }
 
 int DirectSortN::perProduct(size_t batches, size_t chunk, int ind_members) const {
@@ -1639,8 +1681,15 @@ void DirectSortN::checkColumns(const std::string &op, const std::string &noun,
 // columns are shifted by vecRotsOpt, the operator's indicator of a chunk of
 // batches meets the equally shifted columns in one stacked product per column
 // group, and the sums over batches (exact mod q) are folded over the partitions.
+// Tables of Nl and Nr rows walk pairShape's layout: the smaller
+// table's operands, viewed at num_slots, are their own tiling, the rows are taken
+// mod Nl and mod Nr, t runs below min(Nl, Nr), and for Nl < Nr the slots e mod Nl
+// are added up by the residue fold.  Nl = Nr = N issues the square's calls.
 std::vector<CtPtr> DirectSortN::allPairs(const PairOp &op) {
-    const SortShape s = rankShape(N, max_batch);
+    const int Nl = op.n_left ? op.n_left : N, Nr = op.n_right ? op.n_right : N;
+    if (Nl != Nr && (op.sharded || op.offs_eps > 0.0))
+        throw std::logic_error("allPairs: tables of different sizes are unsharded and take no tie-break offsets");
+    const SortShape s = pairShape(Nl, Nr, max_batch);
     const int P = (int)op.cols.size(), Ko = op.ind_members;
     std::optional<AlgoPhase> ph;
     ph.emplace(op.baby_phase);
@@ -1717,12 +1766,14 @@ std::vector<CtPtr> DirectSortN::allPairs(const PairOp &op) {
     std::vector<CtPtr> outs;
     if (P > 0) {
         foldPartitions(out, s);
-        outs = splitMembers(out, P * Ko);
+        foldResidues(out, Nl, Nr);
+        outs = splitMembers(out, P * Ko, Nl);
     }
     if (op.want_count) {
         foldPartitions(cnt, s);
+        foldResidues(cnt, Nl, Nr);
         if (op.closing) op.closing(cnt);
-        for (auto &c : splitMembers(cnt, Ko)) outs.push_back(c);
+        for (auto &c : splitMembers(cnt, Ko, Nl)) outs.push_back(c);
     }
     return outs;
 }
@@ -1970,10 +2021,12 @@ GroupSumLevels groupSumLevels(int key_level, int n, int dg, int df, int ps_split
 // closing mul_const.
 namespace {
 // the two operands of a pair operator: single ciphertexts of one slot count at one level
-void checkPair(const std::string &op, const std::string &noun, const Ciphertext &l, const Ciphertext &r) {
+// (same_slots false: the pair tables have fixed each side's count already)
+void checkPair(const std::string &op, const std::string &noun, const Ciphertext &l, const Ciphertext &r,
+               bool same_slots = true) {
     if (l.batch != 1) throw std::invalid_argument(op + ": the left " + noun + " is a stack");
     if (r.batch != 1) throw std::invalid_argument(op + ": the right " + noun + " is a stack");
-    if (l.slots != r.slots)
+    if (same_slots && l.slots != r.slots)
         throw std::invalid_argument(op + ": the right " + noun + " has " + std::to_string(r.slots) + " slots, the left " +
                                     noun + " " + std::to_string(l.slots));
     if (l.level != r.level)
@@ -1996,13 +2049,18 @@ std::vector<CtPtr> DirectSortN::groupSums(const Ciphertext &kl, const Ciphertext
     const std::string me = "group sum";
     if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
     checkEps(me, eps);
-    checkPair(me, "key", kl, kr);
+    const PairTables tb = pairTables(me, false);
+    checkTableSlots(me, "left_key", kl, true, tb);
+    checkTableSlots(me, "right_key", kr, false, tb);
+    checkPair(me, "key", kl, kr, !tb.set);
     const GroupSumLevels lv =
         groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    checkColumns(me, "the keys", cols, kl.slots, lv.col_max_level);
+    checkColumns(me, tb.set ? "the right table" : "the keys", cols, tb.set ? tb.nr : kl.slots, lv.col_max_level);
     checkDepth(me, "keys at level " + std::to_string(kl.level), lv.out_level, cc.params().L);
     if (!cache_masks) refresh_masks();
     PairOp op{"group_baby", "group_batches", "group_fold"};
+    op.n_left = tb.nl;
+    op.n_right = tb.nr;
     op.left = {&kl};
     op.right = {&kr};
     op.cols = cols;
@@ -2061,14 +2119,19 @@ std::vector<CtPtr> DirectSortN::gatherColumns(const Ciphertext &pl, const Cipher
         if (offsets[k] < -(N - 1) || offsets[k] > N - 1)
             throw std::invalid_argument(me + ": offset " + std::to_string(k) + " (" + std::to_string(offsets[k]) +
                                         ") is outside [-" + std::to_string(N - 1) + ", " + std::to_string(N - 1) + "]");
-    checkPair(me, "position", pl, pr);
+    const PairTables tb = pairTables(me, false);
+    checkTableSlots(me, "pos_l", pl, true, tb);
+    checkTableSlots(me, "pos_r", pr, false, tb);
+    checkPair(me, "position", pl, pr, !tb.set);
     const GatherLevels lv = gatherLevels(pl.level, N, cc.ps_split());
-    checkColumns(me, "the positions", cols, pl.slots, lv.col_max_level);
+    checkColumns(me, tb.set ? "the right table" : "the positions", cols, tb.set ? tb.nr : pl.slots, lv.col_max_level);
     checkDepth(me, "positions at level " + std::to_string(pl.level), P > 0 ? lv.out_level : lv.series_level,
                cc.params().L);
     if (!cache_masks) refresh_masks();
     const std::vector<double> &coeffs = sincCoefficients();
     PairOp op{"gather_baby", "gather_batches", "gather_fold"};
+    op.n_left = tb.nl;
+    op.n_right = tb.nr;
     op.left = {&pl};
     op.right = {&pr};
     op.cols = cols;
@@ -2115,9 +2178,13 @@ std::vector<CtPtr> DirectSortN::runningSums(const Ciphertext &kl, const Cipherte
     if (mode != RunBetween && lo) throw std::invalid_argument(me + ": left_lo, a lower bound, is given outside the between mode");
     if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
     checkEps(me, eps);
-    checkPair(me, "key", kl, kr);
+    const PairTables tb = pairTables(me, mode == RunRows);
+    checkTableSlots(me, "left_key", kl, true, tb);
+    checkTableSlots(me, "right_key", kr, false, tb);
+    checkPair(me, "key", kl, kr, !tb.set);
     if (lo) {
         if (lo->batch != 1) throw std::invalid_argument(me + ": left_lo, the lower bound, is a stack");
+        checkTableSlots(me, "left_lo", *lo, true, tb);
         if (lo->slots != kl.slots)
             throw std::invalid_argument(me + ": left_lo, the lower bound, has " + std::to_string(lo->slots) +
                                         " slots, the left key " + std::to_string(kl.slots));
@@ -2127,11 +2194,13 @@ std::vector<CtPtr> DirectSortN::runningSums(const Ciphertext &kl, const Cipherte
     }
     const GroupSumLevels lv =
         groupSumLevels(kl.level, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    checkColumns(me, "the keys", cols, kl.slots, lv.col_max_level);
+    checkColumns(me, tb.set ? "the right table" : "the keys", cols, tb.set ? tb.nr : kl.slots, lv.col_max_level);
     checkDepth(me, "keys at level " + std::to_string(kl.level), lv.out_level, cc.params().L);
     if (!cache_masks) refresh_masks();
     const bool between = mode == RunBetween;
     PairOp op{"run_baby", "run_batches", "run_fold"};
+    op.n_left = tb.nl;
+    op.n_right = tb.nr;
     op.left = {&kl};
     if (lo) op.left.push_back(lo);
     op.right = {&kr};
@@ -2213,19 +2282,25 @@ std::vector<CtPtr> DirectSortN::windowSums(const std::vector<const Ciphertext *>
         throw std::invalid_argument(me + ": order_lo, a lower bound, is given outside the between mode");
     if (cols.empty() && !want_count) throw std::invalid_argument(me + ": neither a column nor the count is asked for");
     checkEps(me, eps);
+    const PairTables tb = pairTables(me, mode == WinRows);
     std::vector<std::pair<std::string, const Ciphertext *>> keys;
+    std::vector<std::pair<std::string, bool>> args;  // the C ABI's name of each key and its side
     for (int g = 0; g < G; ++g) {
         keys.emplace_back("left partition key " + std::to_string(g), pl[g]);
+        args.emplace_back("part_left[" + std::to_string(g) + "]", true);
         keys.emplace_back("right partition key " + std::to_string(g), pr[g]);
+        args.emplace_back("part_right[" + std::to_string(g) + "]", false);
     }
-    if (ol) keys.emplace_back("left order key", ol);
-    if (orr) keys.emplace_back("right order key", orr);
-    if (olo) keys.emplace_back("lower bound", olo);
+    if (ol) keys.emplace_back("left order key", ol), args.emplace_back("order_left", true);
+    if (orr) keys.emplace_back("right order key", orr), args.emplace_back("order_right", false);
+    if (olo) keys.emplace_back("lower bound", olo), args.emplace_back("order_lo", true);
     for (auto &k : keys)
         if (!k.second) throw std::invalid_argument(me + ": the " + k.first + " is null");
-    for (auto &k : keys) {
+    for (size_t i = 0; i < keys.size(); ++i) {
+        auto &k = keys[i];
         if (k.second->batch != 1) throw std::invalid_argument(me + ": the " + k.first + " is a stack");
-        if (k.second->slots != N)
+        checkTableSlots(me, args[i].first, *k.second, args[i].second, tb);
+        if (!tb.set && k.second->slots != N)
             throw std::invalid_argument(me + ": the " + k.first + " has " + std::to_string(k.second->slots) +
                                         " slots, need " + std::to_string(N));
         if (k.second->level != pl[0]->level || k.second->limbs != pl[0]->limbs)
@@ -2235,13 +2310,15 @@ std::vector<CtPtr> DirectSortN::windowSums(const std::vector<const Ciphertext *>
     }
     const WindowSumLevels lv =
         windowSumLevels(pl[0]->level, F, cfg.compos.n, cfg.compos.dg, cfg.compos.df, cc.ps_split());
-    checkColumns(me, "the keys", cols, N, lv.col_max_level);
+    checkColumns(me, tb.set ? "the right table" : "the keys", cols, tb.nr, lv.col_max_level);
     checkDepth(me, std::to_string(F) + " factors on keys at level " + std::to_string(pl[0]->level), lv.out_level,
                cc.params().L);
     if (!cache_masks) refresh_masks();
     const int V = mode == WinGroup ? 0 : mode == WinBetween ? 2 : 1;  // the order key's sign members per batch
     const double scale_down = 1.0 / (double)(1 << F);
     PairOp op{"win_baby", "win_batches", "win_fold"};
+    op.n_left = tb.nl;
+    op.n_right = tb.nr;
     op.left = pl;  // the partition keys, then the order key and its lower bound
     if (ol) op.left.push_back(ol);
     if (olo) op.left.push_back(olo);

@@ -177,6 +177,16 @@ void directSortSizeParameters(int N, int &multDepth, std::vector<int> &rotations
 void hybridSortSizeParameters(int N, int &multDepth, std::vector<int> &rotations);
 SortShape rankShape(int N, int max_batch);
 SortShape checkShape(int N, int max_batch);
+// The all-pairs layout of a left table of Nl rows against a right table of Nr
+// rows, both powers of two: with N = max(Nl, Nr),
+// n = min(Nl, Nr) and P_ the square shape's partitions for N, P' = min(P_, n)
+// partitions, n / P' batches, N P' slots, np = the square's baby steps for (N, P').
+// Slot s of batch b pairs left row (s mod N) mod Nl with right row
+// (s mod N + t) mod Nr, t = b P' + s / N < n.  Nl = Nr gives rankShape(N, max_batch).
+SortShape pairShape(int Nl, int Nr, int max_batch);
+// rounds of the residue fold that collects a left row's sum from the slots
+// i = e mod Nl when Nl < Nr: log2(Nr / Nl), else 0
+int pairFoldSteps(int Nl, int Nr);
 // Layout of an order-statistic select of k targets over num_slots = N P_ slots
 // (DirectSortN::selectColumns): cap = P_ - 1 targets per member (1 when P_ = 1);
 // target p belongs to member p / cap and owns the cyclic window of N slots from
@@ -468,6 +478,17 @@ class DirectSortN {
     // eps, and |x_i - x_j| + eps <= 1.  No extra depth; the output level is
     // unchanged.
     double tiebreak = 0.0;
+    // Tables of different sizes (0, 0 = off, both tables hold N
+    // rows): groupSums, runningSums, windowSums and gatherColumns pair a left table
+    // of pair_left rows with a right table of pair_right rows, both powers of two
+    // with max(pair_left, pair_right) = N.  Left operands come with pair_left
+    // slots, right operands and columns with pair_right, outputs have pair_left.
+    // The smaller table is viewed at the layout's slot count as it is (a tiling),
+    // the walk runs min / P' batches (pairShape), and for pair_left < pair_right a
+    // residue fold of pairFoldSteps rotations follows the partition fold.  No level
+    // is consumed.  RunRows / WinRows are refused between unequal sizes.  The rank,
+    // the lexicographic rank, the sort and the select do not read it.
+    int pair_left = 0, pair_right = 0;
 
   private:
     struct Lane {
@@ -503,6 +524,7 @@ class DirectSortN {
         bool sharded = false;   // constructRank alone: this rank's batches, then reducePartial
         double offs_eps = 0.0;  // > 0: the tie-break offsets E_b of this eps at offs_level
         int offs_level = 0;
+        int n_left = 0, n_right = 0;  // rows of the two tables (0: N); unequal only without offsets, unsharded
         // the chunk's indicator stack (level asserted by the operator)
         std::function<CtPtr(Engine &, PairChunk &)> indicator;
         // adds the chunk's contribution to the lane's count / present partial
@@ -515,13 +537,27 @@ class DirectSortN {
     };
     // The all-pairs layout every operator of DESIGN.md §6 walks: baby steps,
     // chunks of batches on the lanes, the lanes' partials added on the main
-    // stream, the fold over the partitions.  Returns cols.size() * ind_members
-    // sums, then (want_count) ind_members counts, each of N slots.
+    // stream, the fold over the partitions (then, for n_left < n_right, over the
+    // residues mod n_left).  Returns cols.size() * ind_members sums, then
+    // (want_count) ind_members counts, each of n_left slots.
     std::vector<CtPtr> allPairs(const PairOp &op);
     // add(v, rotate(v, num_slots / 2^i)) over the partitions: the rank's fold
     void foldPartitions(CtPtr &v, const SortShape &s);
-    // the members of a folded stack as single ciphertexts of N slots
-    std::vector<CtPtr> splitMembers(const CtPtr &v, int members);
+    // add(v, rotate(v, Nl 2^k)), k < pairFoldSteps: slot e gathers the slots e mod Nl
+    void foldResidues(CtPtr &v, int Nl, int Nr);
+    // the members of a folded stack as single ciphertexts of `slots` slots (0: N)
+    std::vector<CtPtr> splitMembers(const CtPtr &v, int members, int slots = 0);
+    // The two tables' row counts of a pair operator: (N, N) with the setting off,
+    // else pair_left / pair_right, which must be powers of two >= 2 with the larger
+    // one N; `rows_mode`: the operator's ROWS mode, refused between unequal sizes.
+    struct PairTables {
+        int nl, nr;
+        bool set;
+    };
+    PairTables pairTables(const std::string &op, bool rows_mode) const;
+    // with the setting on: `arg` must hold its table's row count of slots
+    static void checkTableSlots(const std::string &op, const std::string &arg, const Ciphertext &c, bool left,
+                                const PairTables &t);
     // columns per stacked product: the member bound over the largest chunk a lane stacks
     int perProduct(size_t batches, size_t chunk, int ind_members) const;
     // the lane partial of column groups, in column order

@@ -34,6 +34,7 @@ struct fhe_ctx {
     int sort_col_members = 256;  // fhe_set_sort_column_members (initial value: FHE_SORT_COLS_MEMBERS)
     bool mask_cache = true;  // fhe_set_mask_cache
     double sort_tiebreak = 0.0;  // fhe_set_sort_tiebreak
+    int pair_left = 0, pair_right = 0;  // fhe_set_pair_tables
     std::unique_ptr<Engine> kway_lane;  // the k-way sorter's second lane (forked on first use)
     bool kway_stack = false;            // fhe_set_kway_stack (initial value: FHE_KWAY_STACK)
 };
@@ -105,6 +106,8 @@ DirectSortN &sorter_for(fhe_ctx *ctx, int N, const int32_t *rots, int nrot) {
     ds.max_col_members = ctx->sort_col_members;
     ds.cache_masks = ctx->mask_cache;
     ds.tiebreak = ctx->sort_tiebreak;
+    ds.pair_left = ctx->pair_left;
+    ds.pair_right = ctx->pair_right;
     ds.shard_rank = 0;
     ds.shard_world = 1;
     ds.allreduce = nullptr;
@@ -1428,6 +1431,58 @@ int fhe_set_sort_tiebreak(fhe_ctx *ctx, double eps) {
         NEED(ctx);
         if (!(eps >= 0.0 && eps < 0.5)) throw std::invalid_argument("fhe_set_sort_tiebreak: eps must lie in [0, 0.5)");
         ctx->sort_tiebreak = eps;
+    });
+}
+// the row counts of two tables and the ring's slots, as both pair-table entry
+// points refuse them: powers of two >= 2, the larger a size the sort has
+// parameters for, on a ring that holds it
+static SortShape pair_shape_checked(const char *me, int n_left, int n_right, long long ring_slots) {
+    auto pow2 = [](long long v) { return v >= 2 && (v & (v - 1)) == 0; };
+    const std::string pair = "(" + std::to_string(n_left) + ", " + std::to_string(n_right) + ")";
+    if (!pow2(n_left) || !pow2(n_right))
+        throw std::invalid_argument(std::string(me) + ": the row counts must be powers of two >= 2, got " + pair);
+    int depth = 0;
+    std::vector<int> r;
+    try {
+        directSortSizeParameters(std::max(n_left, n_right), depth, r);
+    } catch (const std::invalid_argument &) {
+        throw std::invalid_argument(std::string(me) + ": the larger of " + pair +
+                                    " is not a size fhe_size_parameters knows");
+    }
+    if (!pow2(ring_slots) || ring_slots > (1LL << 30))
+        throw std::invalid_argument(std::string(me) + ": ring_slots must be a power of two, got " +
+                                    std::to_string(ring_slots));
+    try {
+        return pairShape(n_left, n_right, (int)ring_slots);
+    } catch (const std::invalid_argument &) {
+        throw std::invalid_argument(std::string(me) + ": the tables " + pair + " exceed the ring's " +
+                                    std::to_string(ring_slots) + " slots");
+    }
+}
+int fhe_set_pair_tables(fhe_ctx *ctx, int n_left, int n_right) {
+    return guard([&] {
+        if (n_left == 0 && n_right == 0) {
+            NEED(ctx);
+            ctx->pair_left = ctx->pair_right = 0;
+            return;
+        }
+        // the counts alone first (a pure check), then against this context's ring
+        pair_shape_checked("fhe_set_pair_tables", n_left, n_right, 1LL << 30);
+        NEED(ctx);
+        pair_shape_checked("fhe_set_pair_tables", n_left, n_right, (long long)(ctx->eng->n() / 2));
+        ctx->pair_left = n_left;
+        ctx->pair_right = n_right;
+    });
+}
+int fhe_pair_shape(int n_left, int n_right, int ring_slots, int *num_partition, int *num_batch, int *num_slots, int *np,
+                   int *fold_steps) {
+    return guard([&] {
+        const SortShape s = pair_shape_checked("fhe_pair_shape", n_left, n_right, ring_slots);
+        if (num_partition) *num_partition = s.num_partition;
+        if (num_batch) *num_batch = s.num_batch;
+        if (num_slots) *num_slots = s.num_slots;
+        if (np) *np = s.np;
+        if (fold_steps) *fold_steps = pairFoldSteps(n_left, n_right);
     });
 }
 int fhe_tiebreak_offsets(int N, int num_slots, int batch, double eps, double *out) {

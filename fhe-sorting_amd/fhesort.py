@@ -6,6 +6,7 @@ fallback: if the HIP library is missing or no GPU is visible, constructing a
 Context raises.  Method names mirror the reference API where one exists
 (compare, indicator, sign_composite, direct_sort, ...).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -143,6 +144,8 @@ _SIGS = {
     'fhe_mul_plain_sum_groups': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     'fhe_set_sort_tiebreak': (C.c_int, [vp, C.c_double]),
     'fhe_tiebreak_offsets': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, dp]),
+    'fhe_set_pair_tables': (C.c_int, [vp, C.c_int, C.c_int]),
+    'fhe_pair_shape': (C.c_int, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, ip]),
     'fhe_pt_encode_tiebreak': (C.c_int, [vp, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                          C.POINTER(C.c_void_p)]),
     'fhe_sub_add_plain_stacked': (C.c_int, [vp, vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
@@ -500,6 +503,7 @@ class Context:
                  ps_split=None):
         self.logN, self.n, self.L = logN, 1 << logN, L
         self._boots = []
+        self._pair_tables = (0, 0)  # set_pair_tables' current setting
         if _handle is None:
             p = Params(logN, L, scale_bits, first_bits, dnum, seed)
             h = C.c_void_p()
@@ -889,6 +893,33 @@ class Context:
         0 (the default) is the reference's rank."""
         _chk(lib().fhe_set_sort_tiebreak(self.h, float(eps)))
 
+    def set_pair_tables(self, n_left, n_right):
+        """Tables of different sizes (fhe_set_pair_tables): group_sum, running_sum,
+        window_sum and gather called afterwards pair a left table of n_left rows
+        (its keys, bounds and positions in n_left slots) with a right table of
+        n_right rows (its keys, positions and every column in n_right slots), N =
+        max(n_left, n_right), and return outputs of n_left slots, at
+        pair_shape(...)'s batch count.  (0, 0), the default, is the square call."""
+        _chk(lib().fhe_set_pair_tables(self.h, int(n_left), int(n_right)))
+        self._pair_tables = (int(n_left), int(n_right))
+
+    @staticmethod
+    def pair_shape(n_left, n_right, ring_slots):
+        return pair_shape(n_left, n_right, ring_slots)
+
+    @contextlib.contextmanager
+    def _tables(self, tables):
+        """the pair tables of one call: set for its duration, the previous setting restored after it"""
+        if tables is None:
+            yield
+            return
+        prev = self._pair_tables
+        self.set_pair_tables(*tables)
+        try:
+            yield
+        finally:
+            self.set_pair_tables(*prev)
+
     def encode_tiebreak(self, batches, num_slots, N, eps, level):
         """fhe_pt_encode_tiebreak: the offsets of the given comparator batches,
         filled and encoded on the device as one batch"""
@@ -906,7 +937,7 @@ class Context:
             raise ValueError('sub_add_plain_stacked: one plaintext per operand')
         return self._new(lib().fhe_sub_add_plain_stacked, a.h, ba, pa, len(bs))
 
-    def group_sum(self, left_key, right_key, cols, eps, N, rots, cfg, count=False):
+    def group_sum(self, left_key, right_key, cols, eps, N, rots, cfg, count=False, tables=None):
         """Group sums and lookups (fhe_direct_group_sum): out[p] has N slots, slot e
         holds the sum of cols[p] over the right rows j with |left_key_e - right_key_j|
         < eps.  right_key = left_key: SUM(v) OVER (PARTITION BY key), the row itself
@@ -915,16 +946,19 @@ class Context:
         the number of matching right rows.  Equal keys must agree far below eps,
         distinct keys differ by >= 2 eps, |difference| + eps <= 1, and the sign
         configuration must resolve eps; 0 < eps < 0.5.  A column may sit at
-        group_sum_levels(...)[0] at most; the outputs end at the rank's level."""
+        group_sum_levels(...)[0] at most; the outputs end at the rank's level.
+        tables=(Nl, Nr): set_pair_tables for this call -- left_key in Nl slots, right_key
+        and cols in Nr, N = max(Nl, Nr), outputs of Nl slots."""
         r = np.asarray(rots, dtype=np.int32)
         cols = list(cols)
         arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
         outs = (C.c_void_p * max(1, len(cols)))()
         cnt = C.c_void_p()
-        _chk(lib().fhe_direct_group_sum(self.h, None if left_key is None else left_key.h,
-                                        None if right_key is None else right_key.h, arr, len(cols), float(eps), N,
-                                        _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
-                                        C.byref(cnt) if count else None))
+        with self._tables(tables):
+            _chk(lib().fhe_direct_group_sum(self.h, None if left_key is None else left_key.h,
+                                            None if right_key is None else right_key.h, arr, len(cols), float(eps), N,
+                                            _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
+                                            C.byref(cnt) if count else None))
         res = [Ct(self, outs[i]) for i in range(len(cols))]
         return (res, Ct(self, cnt.value)) if count else res
 
@@ -944,7 +978,7 @@ class Context:
         mul(add(member(a, z), member(a_add, z)), member(b_stack, p * B + z)) word for word"""
         return self._new(lib().fhe_mul_pairs, a.h, a_add.h, b_stack.h, ncols)
 
-    def gather(self, pos_l, pos_r, cols, offsets, N, rots, present=False, sum_offsets=False):
+    def gather(self, pos_l, pos_r, cols, offsets, N, rots, present=False, sum_offsets=False, tables=None):
         """Gather by encrypted position (fhe_direct_gather): for column p and offset k
         the output has N slots, slot e holds cols[p] at the right row j whose position
         pos_r[j] equals pos_l[e] + offsets[k], zero where there is none.  The positions
@@ -953,7 +987,9 @@ class Context:
         present=True returns (outs, flags), flags[k] holding 1 where the neighbour
         exists.  sum_offsets=True adds the offsets' indicators before the product: one
         output per column, the sum over the offsets (ROWS BETWEEN), and one flag, the
-        frame's row count.  A column may sit at gather_levels(...)[0] at most."""
+        frame's row count.  A column may sit at gather_levels(...)[0] at most.
+        tables=(Nl, Nr): set_pair_tables for this call -- pos_l in Nl slots, pos_r and
+        cols in Nr, N = max(Nl, Nr), outputs of Nl slots."""
         r = np.asarray(rots, dtype=np.int32)
         off = np.asarray(list(offsets), dtype=np.int32)
         cols = list(cols)
@@ -961,9 +997,10 @@ class Context:
         nout = (len(cols) + (1 if present else 0)) * ko
         arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
         outs = (C.c_void_p * max(1, nout))()
-        _chk(lib().fhe_direct_gather(self.h, None if pos_l is None else pos_l.h, None if pos_r is None else pos_r.h,
-                                     arr, len(cols), _int(off), len(off), int(bool(present)), int(bool(sum_offsets)),
-                                     N, _int(r), len(r), outs))
+        with self._tables(tables):
+            _chk(lib().fhe_direct_gather(self.h, None if pos_l is None else pos_l.h,
+                                         None if pos_r is None else pos_r.h, arr, len(cols), _int(off), len(off),
+                                         int(bool(present)), int(bool(sum_offsets)), N, _int(r), len(r), outs))
         res = [Ct(self, outs[i]) for i in range(nout)]
         return (res[:len(cols) * ko], res[len(cols) * ko:]) if present else res
 
@@ -994,7 +1031,8 @@ class Context:
         for word"""
         return self._new(lib().fhe_mul_gather, a_stack.h, b_stack.h, ncols, noffsets)
 
-    def running_sum(self, left_key, right_key, cols, eps, N, rots, cfg, mode=RUN_ROWS, lo=None, count=False):
+    def running_sum(self, left_key, right_key, cols, eps, N, rots, cfg, mode=RUN_ROWS, lo=None, count=False,
+                    tables=None):
         """Running sums (fhe_direct_running_sum): out[p] has N slots, slot e holds the
         sum of cols[p] over the right rows j that the mode selects for left row e:
         RUN_ROWS the rows up to and including e in the stable key order (right_key =
@@ -1007,17 +1045,21 @@ class Context:
         right rows; with RUN_ROWS and right_key = left_key, count - 1 is the stable
         rank.  Equal keys must agree far below eps, distinct keys and bounds differ
         by >= 2 eps, every difference +- eps lie in [-1, 1], and the sign
-        configuration must resolve eps; 0 < eps < 0.5.  Levels are group_sum_levels'."""
+        configuration must resolve eps; 0 < eps < 0.5.  Levels are group_sum_levels'.
+        tables=(Nl, Nr): set_pair_tables for this call -- left_key and lo in Nl slots,
+        right_key and cols in Nr, N = max(Nl, Nr), outputs of Nl slots; RUN_ROWS is
+        refused between unequal sizes."""
         r = np.asarray(rots, dtype=np.int32)
         cols = list(cols)
         arr = (C.c_void_p * max(1, len(cols)))(*[None if c is None else c.h for c in cols])
         outs = (C.c_void_p * max(1, len(cols)))()
         cnt = C.c_void_p()
-        _chk(lib().fhe_direct_running_sum(self.h, None if left_key is None else left_key.h,
-                                          None if lo is None else lo.h,
-                                          None if right_key is None else right_key.h, arr, len(cols), int(mode),
-                                          float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
-                                          C.byref(cnt) if count else None))
+        with self._tables(tables):
+            _chk(lib().fhe_direct_running_sum(self.h, None if left_key is None else left_key.h,
+                                              None if lo is None else lo.h,
+                                              None if right_key is None else right_key.h, arr, len(cols), int(mode),
+                                              float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2], outs,
+                                              C.byref(cnt) if count else None))
         res = [Ct(self, outs[i]) for i in range(len(cols))]
         return (res, Ct(self, cnt.value)) if count else res
 
@@ -1093,7 +1135,7 @@ class Context:
         return self._new(lib().fhe_mul_lex, t.h, float(t_const), u.h, w.h)
 
     def window_sum(self, part_left, part_right, cols, eps, N, rots, cfg, order_left=None, order_right=None,
-                   mode=WIN_GROUP, lo=None, count=False):
+                   mode=WIN_GROUP, lo=None, count=False, tables=None):
         """Window sums (fhe_direct_window_sum): out[p] has N slots, slot e holds the sum
         of cols[p] over the right rows j that agree with left row e on every partition
         key (part_left[g]_e = part_right[g]_j, 1 to 3 keys; the same handles for a self
@@ -1104,7 +1146,10 @@ class Context:
         partition keys) is GROUP BY a, b and the join on several keys.  count=True:
         returns (outs, count), the number of selected right rows (ROW_NUMBER() under
         WIN_ROWS).  running_sum's conditions hold for every key; levels are
-        window_sum_levels(key_level, len(part_left) + (mode != WIN_GROUP), cfg)."""
+        window_sum_levels(key_level, len(part_left) + (mode != WIN_GROUP), cfg).
+        tables=(Nl, Nr): set_pair_tables for this call -- part_left, order_left and lo in
+        Nl slots, part_right, order_right and cols in Nr, N = max(Nl, Nr), outputs of Nl
+        slots; WIN_ROWS is refused between unequal sizes."""
         r = np.asarray(rots, dtype=np.int32)
         cols, part_left, part_right = list(cols), list(part_left), list(part_right)
         if len(part_left) != len(part_right):
@@ -1115,9 +1160,10 @@ class Context:
         arr = (C.c_void_p * max(1, len(cols)))(*[h(c) for c in cols])
         outs = (C.c_void_p * max(1, len(cols)))()
         cnt = C.c_void_p()
-        _chk(lib().fhe_direct_window_sum(self.h, pl, pr, len(part_left), h(order_left), h(lo), h(order_right), arr,
-                                         len(cols), int(mode), float(eps), N, _int(r), len(r), cfg[0], cfg[1], cfg[2],
-                                         outs, C.byref(cnt) if count else None))
+        with self._tables(tables):
+            _chk(lib().fhe_direct_window_sum(self.h, pl, pr, len(part_left), h(order_left), h(lo), h(order_right),
+                                             arr, len(cols), int(mode), float(eps), N, _int(r), len(r), cfg[0],
+                                             cfg[1], cfg[2], outs, C.byref(cnt) if count else None))
         res = [Ct(self, outs[i]) for i in range(len(cols))]
         return (res, Ct(self, cnt.value)) if count else res
 
@@ -1484,6 +1530,18 @@ def select_layout(N, num_slots, ntargets):
     if m < 0:
         raise FheError(-m, lib().fhe_last_error().decode())
     return m, [int(x) for x in member], [int(x) for x in start]
+
+
+def pair_shape(n_left, n_right, ring_slots):
+    """fhe_pair_shape (pure host): (num_slots, num_partition, num_batch, np, fold_steps)
+    of an all-pairs call between tables of n_left and n_right rows on a ring of
+    ring_slots = n / 2 slots; the first four in stable_model.rank_shape's order"""
+    v = [C.c_int() for _ in range(5)]
+    rc = lib().fhe_pair_shape(int(n_left), int(n_right), int(ring_slots), *[C.byref(x) for x in v])
+    if rc != FHE_OK:
+        raise FheError(rc, lib().fhe_last_error().decode())
+    P, nb, S, npb, fold = (x.value for x in v)
+    return S, P, nb, npb, fold
 
 
 def tiebreak_offsets(N, num_slots, batch, eps):

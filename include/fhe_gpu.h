@@ -376,6 +376,35 @@ int fhe_mul_plain_sum_groups(fhe_ctx *ctx, const fhe_ct *stack, const fhe_pt *co
  * used as given.  The offset plaintexts are cached per context like the masks
  * (fhe_set_mask_cache(ctx, 0): re-encoded at the start of every rank). */
 int fhe_set_sort_tiebreak(fhe_ctx *ctx, double eps);
+/* Tables of different sizes in the all-pairs operators (the project's own
+ * extension).  (0, 0), the default: every call behaves word for
+ * word as before, both tables holding N rows in N slots.  With (n_left, n_right)
+ * set, fhe_direct_group_sum, fhe_direct_running_sum, fhe_direct_window_sum and
+ * fhe_direct_gather pair a left table of n_left rows with a right table of
+ * n_right rows: they require N == max(n_left, n_right), the left operands
+ * (left_key, left_lo, part_left[], order_left, order_lo, pos_l) with n_left slots,
+ * the right operands and every column with n_right slots, and return outputs of
+ * n_left slots; rots stay fhe_size_parameters(N)'s and no level is consumed
+ * beyond the square call's.  The walk costs min(n_left, n_right) / P' comparator
+ * batches (fhe_pair_shape) where the square one costs N / P_.  (N, N) gives the
+ * square call's words.  FHE_EINVAL: a count that is no power of two or below 2,
+ * max(n_left, n_right) not a size fhe_size_parameters knows or above the ring's
+ * n / 2 slots; at call time N != max(n_left, n_right), an operand whose slot count
+ * does not fit (the message names the argument and both counts), and
+ * FHE_RUN_ROWS / FHE_WIN_ROWS under n_left != n_right.  fhe_direct_sort*,
+ * fhe_direct_select and fhe_direct_lex_rank do not read the setting. */
+int fhe_set_pair_tables(fhe_ctx *ctx, int n_left, int n_right);
+/* pure host: the layout of such a call on a ring of ring_slots = n / 2 slots.
+ * With N = max, m = min of the counts and P_ = min(N, ring_slots / N):
+ * num_partition = P' = min(P_, m), num_batch = m / P', num_slots = N P', np the
+ * baby steps of (N, P'), fold_steps = log2(n_right / n_left) rounds of the
+ * residue fold when n_left < n_right, else 0.  Slot s of batch b pairs left row
+ * (s mod N) mod n_left with right row (s mod N + t) mod n_right, t = b P' + s / N.
+ * n_left == n_right gives the rank's shape.  Any pointer may be NULL.
+ * FHE_EINVAL as fhe_set_pair_tables, and for a ring_slots that is no power of
+ * two. */
+int fhe_pair_shape(int n_left, int n_right, int ring_slots, int *num_partition, int *num_batch, int *num_slots,
+                   int *np, int *fold_steps);
 /* pure host: the offsets of comparator batch `batch` over num_slots = N P_ slots
  * (N and P_ powers of two, P_ <= N, 0 <= batch < N / P_).  Slot s compares element
  * e = s mod N with element (e + t) mod N, t = batch P_ + s / N; out[s] = +eps where
@@ -429,7 +458,15 @@ int fhe_sub_add_plain_stacked(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *const
  * levels, eps outside (0, 0.5), ncols < 0, a null column, and ncols == 0 without
  * count_out; FHE_EDEPTH, before any work, for a column above col_max_level and
  * for a context without out_level levels.  On failure no output handle is set
- * (every one is NULL). */
+ * (every one is NULL).
+ * Tables of different sizes (fhe_set_pair_tables(ctx, Nl, Nr), N = max(Nl, Nr)):
+ * left_key has Nl slots, right_key and every column Nr, the outputs Nl, at
+ * min(Nl, Nr) / P' comparator batches (fhe_pair_shape) instead of N / P_ and at
+ * the same levels.  GROUP BY over a known domain is the call with the domain's
+ * values as left_key.
+ * Tables whose row count is no power of two are padded to one: sentinel keys at
+ * least 2 eps from every real key and zero columns; such rows match nothing and
+ * add nothing, to the counts either. */
 int fhe_direct_group_sum(fhe_ctx *ctx, const fhe_ct *left_key, const fhe_ct *right_key, const fhe_ct *const *cols,
                          int ncols, double eps, int N, const int32_t *rots, int nrot, int n, int dg, int df,
                          fhe_ct **outs /* ncols handles */, fhe_ct **count_out /* may be NULL */);
@@ -492,7 +529,16 @@ int fhe_mul_pairs(fhe_ctx *ctx, const fhe_ct *a, const fhe_ct *a_add, const fhe_
  * positions at different levels, ncols < 0, a null column, noffsets < 1, an offset
  * outside [-(N - 1), N - 1], and ncols == 0 without want_present; FHE_EDEPTH, before
  * any work, for a column above col_max_level and for a context without the
- * levels.  On failure no output handle is set (every one is NULL). */
+ * levels.  On failure no output handle is set (every one is NULL).
+ * Tables of different sizes (fhe_set_pair_tables(ctx, Nl, Nr), N = max(Nl, Nr)):
+ * pos_l has Nl slots, pos_r and every column Nr, the outputs Nl; positions,
+ * offsets and the series' table stay those of N, so fhe_gather_levels(.., N)
+ * holds.  Nl queries into a table of Nr rows cost min(Nl, Nr) / P' batches
+ * (fhe_pair_shape).
+ * Tables whose row count is no power of two are padded to one: sentinel
+ * positions no real position plus an offset reaches (right rows) or that reach
+ * no right row (left rows) and zero columns; such rows match nothing and add
+ * nothing, to the present flags either. */
 int fhe_direct_gather(fhe_ctx *ctx, const fhe_ct *pos_l, const fhe_ct *pos_r, const fhe_ct *const *cols, int ncols,
                       const int32_t *offsets, int noffsets, int want_present, int sum_offsets, int N,
                       const int32_t *rots, int nrot, fhe_ct **outs);
@@ -558,7 +604,16 @@ int fhe_mul_gather(fhe_ctx *ctx, const fhe_ct *a_stack, const fhe_ct *b_stack, i
  * left_lo given outside FHE_RUN_BETWEEN or missing in it, and a left_lo that is a
  * stack or differs from left_key in level or slot count; FHE_EDEPTH, before any
  * work, for a column above col_max_level and for a context without out_level
- * levels.  On failure no output handle is set (every one is NULL). */
+ * levels.  On failure no output handle is set (every one is NULL).
+ * Tables of different sizes (fhe_set_pair_tables(ctx, Nl, Nr), N = max(Nl, Nr)):
+ * left_key and left_lo have Nl slots, right_key and every column Nr, the outputs
+ * Nl, at min(Nl, Nr) / P' comparator batches (fhe_pair_shape) and the same
+ * levels: Nl query keys searched in Nr sorted keys, the band join.  FHE_RUN_ROWS
+ * is FHE_EINVAL under Nl != Nr: its tie-break by index has no meaning between
+ * tables of different length.
+ * Tables whose row count is no power of two are padded to one: sentinel keys at
+ * least 2 eps from every real key and bound and zero columns; such rows match nothing and
+ * add nothing, to the counts either. */
 #define FHE_RUN_ROWS 0
 #define FHE_RUN_LE 1
 #define FHE_RUN_LT 2
@@ -689,7 +744,16 @@ int fhe_mul_lex(fhe_ctx *ctx, const fhe_ct *t, double t_const, const fhe_ct *u, 
  * stack, keys at different levels or with a slot count other than N, a column with
  * another slot count, ncols < 0, nothing asked for, and eps outside (0, 0.5);
  * FHE_EDEPTH, before any work, for a column above col_max_level and for a context
- * without out_level levels.  On failure no output handle is set (every one is NULL). */
+ * without out_level levels.  On failure no output handle is set (every one is NULL).
+ * Tables of different sizes (fhe_set_pair_tables(ctx, Nl, Nr), N = max(Nl, Nr)):
+ * part_left[], order_left and order_lo have Nl slots, part_right[], order_right and
+ * every column Nr, the outputs Nl, at min(Nl, Nr) / P' comparator batches
+ * (fhe_pair_shape) and the same levels: the as-of join of a small table against
+ * a large one, GROUP BY a, b as one row per group.  FHE_WIN_ROWS is FHE_EINVAL
+ * under Nl != Nr.
+ * Tables whose row count is no power of two are padded to one: sentinel partition keys at
+ * least 2 eps from every real key and zero columns; such rows match nothing and
+ * add nothing, to the counts either. */
 #define FHE_WIN_ROWS 0
 #define FHE_WIN_LE 1
 #define FHE_WIN_LT 2
