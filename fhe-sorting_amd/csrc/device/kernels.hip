@@ -194,99 +194,133 @@ __global__ __launch_bounds__(NT) void k_mul_plain(u64 *out, const u64 *a, const 
     const ulonglong2 x = ld2(a + oa), y = ld2(p + ob);
     st2(out + oo, make_ulonglong2(mul_barrett(x.x, y.x, m), mul_barrett(x.y, y.y, m)));
 }
-// member z: a, b [2][limbs][n] at z * sa / z * sb (sb = 0 broadcasts b);
-// d01 [members][2][limbs][n], d2 [members][limbs][n]
-// a2 (optional, member stride sa2): a + a2 is the left operand (the PS node's
-// T_{k 2^j} + c(u), formed on load instead of in a separate pass)
-__global__ __launch_bounds__(NT) void k_tensor(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
-                                               size_t sa, size_t sb, const u64 *a2, size_t sa2, const Mod *mods,
-                                               int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
-    const u64 *A = a + z * sa, *Bp = b + z * sb;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    if (a2) {
-        const u64 *A2 = a2 + z * sa2;
-        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
-        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
-        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
-    }
-    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
-    ulonglong2 e0, e1, e2;
-    e0.x = mul_barrett(a0.x, b0.x, m);
-    e0.y = mul_barrett(a0.y, b0.y, m);
-    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-    st2(d01 + z * 2 * ln_all + o, e0);
-    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
-    st2(d2 + z * ln_all + o, e2);
-}
-// k_tensor with mul_add's summands folded into (d0, d1) (round 5): d_p of member z
-// += sum_i (K_i 2^sh_i mod q_l) x_i[2 z + p] -- the same lazy 128-bit sum and one
-// reduction as k_linear_sum accumulating into d01 after the tensor, so the words
-// are unchanged, without that pass's re-read and re-write of d01 (4 of its
-// 2 (M + 2) limb-units per member).  M <= TL_MAX summands of one limb count.
-constexpr int TL_MAX = 4;
-struct TensorLin {
-    const u64 *x[TL_MAX];
-    int64_t K[TL_MAX];
-    uint8_t sh[TL_MAX];
-    size_t xseg;  // segment stride of the summands (segment 2 member + poly)
+// ------------------------------ tensor products and stacked differences ----
+// The pieces every k_tensor* and k_sub_*_stacked kernel is composed of
+// (DESIGN.md §4); each idea is written once here.
+//
+// The coordinates of a two-coefficient thread: limb l, whether its pair k, k + 1
+// lies inside the ring, and the pair's word offset o = l n + k inside one polynomial.
+struct Coord {
+    size_t n, k;
+    int l;
+    bool in;
+    __device__ __forceinline__ size_t o() const { return (size_t)l * n + k; }
 };
-template <int M>
-__global__ __launch_bounds__(NT) void k_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
-                                                   size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorLin L,
-                                                   const Mod *mods, int logN) {
-    __shared__ u64 w[TL_MAX];
+__device__ __forceinline__ Coord coord(int logN) {
     const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const Mod m = mods[l];
-    if ((int)threadIdx.x < M) w[threadIdx.x] = smod(L.K[threadIdx.x], L.sh[threadIdx.x], m);
-    __syncthreads();
     const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
-    const u64 *A = a + z * sa, *Bp = b + z * sb;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    if (a2) {
-        const u64 *A2 = a2 + z * sa2;
-        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
-        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
-        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
-    }
-    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
-    ulonglong2 xs[2][M];  // the summands' loads issued with the operands'
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int i = 0; i < M; ++i) xs[p][i] = ld2(L.x[i] + (2 * z + p) * L.xseg + o);
-    Acc128 r[2][2];
-    r[0][0].lo = mul_barrett(a0.x, b0.x, m);
-    r[0][1].lo = mul_barrett(a0.y, b0.y, m);
-    r[1][0].lo = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    r[1][1].lo = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    ulonglong2 e2;
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            mac128(r[p][0], xs[p][i].x, w[i]);
-            mac128(r[p][1], xs[p][i].y, w[i]);
-        }
-        st2(d01 + z * 2 * ln_all + p * ln_all + o, make_ulonglong2(reduce128(r[p][0], m), reduce128(r[p][1], m)));
-    }
-    st2(d2 + z * ln_all + o, e2);
+    return {n, k, (int)blockIdx.y, k < n};
 }
-// k_tensor / k_tensor_lin<M> with constants (Engine::mul_add's a_const, out_const).
-// They are kernels of their own, so the plain forms above keep their code and registers.
+__device__ __forceinline__ ulonglong2 add2(ulonglong2 x, ulonglong2 y, u64 q) {
+    return make_ulonglong2(add_mod(x.x, y.x, q), add_mod(x.y, y.y, q));
+}
+__device__ __forceinline__ ulonglong2 add2(ulonglong2 x, u64 w, u64 q) {
+    return make_ulonglong2(add_mod(x.x, w, q), add_mod(x.y, w, q));
+}
+__device__ __forceinline__ ulonglong2 sub2(ulonglong2 x, ulonglong2 y, u64 q) {
+    return make_ulonglong2(sub_mod(x.x, y.x, q), sub_mod(x.y, y.y, q));
+}
+__device__ __forceinline__ ulonglong2 neg2(ulonglong2 x, u64 q) {
+    return make_ulonglong2(sub_mod(0, x.x, q), sub_mod(0, x.y, q));
+}
+// A ciphertext at this thread: the word pairs of c0 and c1 ([2][limbs][n] at base)
+struct Ct {
+    ulonglong2 c0, c1;
+    static __device__ __forceinline__ Ct load(const u64 *base, size_t ln_all, size_t o) {
+        return {ld2(base + o), ld2(base + ln_all + o)};
+    }
+    __device__ __forceinline__ void store(u64 *base, size_t ln_all, size_t o) const {
+        st2(base + o, c0);
+        st2(base + ln_all + o, c1);
+    }
+};
+__device__ __forceinline__ Ct add(const Ct &x, const Ct &y, u64 q) { return {add2(x.c0, y.c0, q), add2(x.c1, y.c1, q)}; }
+__device__ __forceinline__ Ct sub(const Ct &x, const Ct &y, u64 q) { return {sub2(x.c0, y.c0, q), sub2(x.c1, y.c1, q)}; }
+__device__ __forceinline__ Ct neg(const Ct &x, u64 q) { return {neg2(x.c0, q), neg2(x.c1, q)}; }
+// x with a constant's residue, or a plaintext's word pair, added to c0
+__device__ __forceinline__ Ct add_c0(const Ct &x, u64 w, u64 q) { return {add2(x.c0, w, q), x.c1}; }
+__device__ __forceinline__ Ct add_c0(const Ct &x, ulonglong2 p, u64 q) { return {add2(x.c0, p, q), x.c1}; }
+// The tensor product (a0 b0, a0 b1 + a1 b0, a1 b1) of two ciphertexts, and its
+// place in member mo of d01 [members][2][limbs][n] and d2 [members][limbs][n]
+struct Tensor {
+    ulonglong2 e0, e1, e2;
+    __device__ __forceinline__ void store(u64 *d01, u64 *d2, size_t ln_all, size_t mo, size_t o) const {
+        st2(d01 + mo * 2 * ln_all + o, e0);
+        st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
+        st2(d2 + mo * ln_all + o, e2);
+    }
+};
+__device__ __forceinline__ Tensor tensor(const Ct &a, const Ct &b, const Mod &m) {
+    Tensor e;
+    e.e0.x = mul_barrett(a.c0.x, b.c0.x, m);
+    e.e0.y = mul_barrett(a.c0.y, b.c0.y, m);
+    e.e1.x = add_mod(mul_barrett(a.c0.x, b.c1.x, m), mul_barrett(a.c1.x, b.c0.x, m), m.q);
+    e.e1.y = add_mod(mul_barrett(a.c0.y, b.c1.y, m), mul_barrett(a.c1.y, b.c0.y, m), m.q);
+    e.e2.x = mul_barrett(a.c1.x, b.c1.x, m);
+    e.e2.y = mul_barrett(a.c1.y, b.c1.y, m);
+    return e;
+}
+// The tiled form of the tensor kernels: one fixed operand against the up to T
+// tiled operands j0 .. j0 + T - 1 (J of them in all, so the last tile is
+// guarded), every tiled operand's loads issued ahead of the arithmetic.  The
+// kernels differ in three things: fixed() forms the fixed operand from words
+// its caller has loaded, at(j) is where tiled operand j lives, member(j) the
+// output member the product lands in.  TILED_LEFT puts the tiled operand on
+// the product's left.
+template <int T, bool TILED_LEFT, typename Fixed, typename At, typename Member>
+__device__ __forceinline__ void tensor_tiled(u64 *d01, u64 *d2, size_t ln_all, size_t o, const Mod &m, int j0, int J,
+                                             Fixed fixed, At at, Member member) {
+    Ct t[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (j0 + j < J) t[j] = Ct::load(at(j0 + j), ln_all, o);
+    const Ct x = fixed();
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (j0 + j < J) {
+            if constexpr (TILED_LEFT)
+                tensor(t[j], x, m).store(d01, d2, ln_all, member(j0 + j), o);
+            else
+                tensor(x, t[j], m).store(d01, d2, ln_all, member(j0 + j), o);
+        }
+}
+// The column tile of a column-major stack of `members`-member columns: grid
+// z = group * members + z, p0 the first of the group's PC columns
+struct ColTile {
+    int z, p0;
+};
+template <int PC>
+__device__ __forceinline__ ColTile col_tile(int members) {
+    return {(int)(blockIdx.z % (unsigned)members), (int)(blockIdx.z / (unsigned)members) * PC};
+}
+// One tile of a stacked difference: the SUB_TILE right operands m0 .. m0 + TM - 1
+// of a launch's B, loaded at the clamped index (a last tile narrower than TM
+// repeats its last operand) ahead of the arithmetic, with their plaintexts when
+// the kernel takes any; each(emit) calls emit(t, member) for the valid t only.
+// m0 and B are block-uniform.
+struct SubTile {
+    static constexpr int TM = SUB_TILE;
+    int m0, B;
+    Ct b[TM];
+    ulonglong2 p[TM];
+    __device__ __forceinline__ int clamped(int t) const { return min(m0 + t, B - 1); }
+    __device__ __forceinline__ void load(const u64 *const *bs, size_t ln_all, size_t o) {
+#pragma unroll
+        for (int t = 0; t < TM; ++t) b[t] = Ct::load(bs[clamped(t)], ln_all, o);
+    }
+    __device__ __forceinline__ void load_plain(const u64 *const *ps, size_t o) {
+#pragma unroll
+        for (int t = 0; t < TM; ++t) p[t] = ld2(ps[clamped(t)] + o);
+    }
+    template <typename Emit>
+    __device__ __forceinline__ void each(Emit emit) const {
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            if (m0 + t < B) emit(t, m0 + t);
+    }
+};
+
+// The constants of k_tensor_c / k_tensor_lin_c<M> (Engine::mul_add's a_const, out_const).
 // C.aK (0 = none): the constant aK 2^ash is added to the left operand's c0 after
 // a2 (the PS node's T_{k 2^j} + c0: add_const's words without its pass).
 // C.oK (0 = none): the constant oK 2^osh, at the product's scale after its
@@ -303,98 +337,139 @@ __device__ __forceinline__ u64 tensor_out_const(int64_t K, int sh, const Mod &m,
     const int last = (int)gridDim.y - 1;
     return l == last ? 0 : mul_barrett(smod(K, sh, m), reduce64(mods[last].q, m), m);
 }
+// a (+ a2) of member z: the left operand of the member-wise kernels
+__device__ __forceinline__ Ct tensor_left(const u64 *A, const u64 *a2, size_t sa2, size_t z, size_t ln_all, size_t o,
+                                          u64 q) {
+    Ct x = Ct::load(A, ln_all, o);
+    if (a2) x = add(x, Ct::load(a2 + z * sa2, ln_all, o), q);
+    return x;
+}
+// The member-wise form of k_tensor and k_tensor_c: form the left operand, load
+// the right one, take the product, store.  CONSTS adds C's two constants, formed
+// once per block in LDS.  The constants are kernels of their own (k_tensor_c),
+// so the plain form keeps its code and registers.
+template <bool CONSTS>
+__device__ __forceinline__ void tensor_members(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all, size_t sa,
+                                               size_t sb, const u64 *a2, size_t sa2, const TensorConst &C,
+                                               const Mod *mods, int logN) {
+    __shared__ u64 wc[2];  // the left operand's constant and d0's; unused, and not allocated, without CONSTS
+    const Coord c = coord(logN);
+    if constexpr (CONSTS) {
+        const Mod m = mods[c.l];
+        if (threadIdx.x == 0) wc[0] = smod(C.aK, C.ash, m);
+        if (threadIdx.x == 1) wc[1] = C.oK ? tensor_out_const(C.oK, C.osh, m, mods, c.l) : 0;
+        __syncthreads();
+    }
+    if (!c.in) return;
+    const Mod m = mods[c.l];
+    const size_t z = blockIdx.z, o = c.o();
+    const u64 *A = a + z * sa, *Bp = b + z * sb;
+    Ct x = tensor_left(A, a2, sa2, z, ln_all, o, m.q);
+    if constexpr (CONSTS) x = add_c0(x, wc[0], m.q);
+    Tensor e = tensor(x, Ct::load(Bp, ln_all, o), m);
+    if constexpr (CONSTS) e.e0 = add2(e.e0, wc[1], m.q);
+    e.store(d01, d2, ln_all, z, o);
+}
+// member z: a, b [2][limbs][n] at z * sa / z * sb (sb = 0 broadcasts b);
+// d01 [members][2][limbs][n], d2 [members][limbs][n]
+// a2 (optional, member stride sa2): a + a2 is the left operand (the PS node's
+// T_{k 2^j} + c(u), formed on load instead of in a separate pass)
+__global__ __launch_bounds__(NT) void k_tensor(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
+                                               size_t sa, size_t sb, const u64 *a2, size_t sa2, const Mod *mods,
+                                               int logN) {
+    tensor_members<false>(d01, d2, a, b, ln_all, sa, sb, a2, sa2, TensorConst{}, mods, logN);
+}
 __global__ __launch_bounds__(NT) void k_tensor_c(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
                                                  size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorConst C,
                                                  const Mod *mods, int logN) {
-    __shared__ u64 wc[2];
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const Mod m = mods[l];
-    if (threadIdx.x == 0) wc[0] = smod(C.aK, C.ash, m);
-    if (threadIdx.x == 1) wc[1] = C.oK ? tensor_out_const(C.oK, C.osh, m, mods, l) : 0;
-    __syncthreads();
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
-    const u64 *A = a + z * sa, *Bp = b + z * sb;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    if (a2) {
-        const u64 *A2 = a2 + z * sa2;
-        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
-        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
-        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
-    }
-    const u64 wa = wc[0], wo = wc[1];
-    a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
-    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
-    ulonglong2 e0, e1, e2;
-    e0.x = add_mod(mul_barrett(a0.x, b0.x, m), wo, m.q);
-    e0.y = add_mod(mul_barrett(a0.y, b0.y, m), wo, m.q);
-    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-    st2(d01 + z * 2 * ln_all + o, e0);
-    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
+    tensor_members<true>(d01, d2, a, b, ln_all, sa, sb, a2, sa2, C, mods, logN);
+}
+// k_tensor with mul_add's summands folded into (d0, d1) (round 5): d_p of member z
+// += sum_i (K_i 2^sh_i mod q_l) x_i[2 z + p] -- the same lazy 128-bit sum and one
+// reduction as k_linear_sum accumulating into d01 after the tensor, so the words
+// are unchanged, without that pass's re-read and re-write of d01 (4 of its
+// 2 (M + 2) limb-units per member).  M <= TL_MAX summands of one limb count.
+constexpr int TL_MAX = 4;
+struct TensorLin {
+    const u64 *x[TL_MAX];
+    int64_t K[TL_MAX];
+    uint8_t sh[TL_MAX];
+    size_t xseg;  // segment stride of the summands (segment 2 member + poly)
+};
+// The sums and stores of the lin forms, given x, y, xs, w, m, z, o in scope: e0 and e1
+// start the 128-bit sums of d0 and d1; each is reduced and stored before the next
+// begins, so neither is live across the other (that is why they do not go
+// through Tensor::store).  D0_CONST: a statement on v, d0's reduced pair.
+// A macro like EW_PROLOGUE, not a function: written as an inlined function this
+// tail costs k_tensor_lin<3> and <4> a wave per SIMD
+// (profiles/kernel_bodies/isa_table.md).
+#define TENSOR_LIN_SUMS(D0_CONST)                                                                        \
+    const Tensor e = tensor(x, y, m);                                                                    \
+    Acc128 r[2][2];                                                                                      \
+    r[0][0].lo = e.e0.x;                                                                                 \
+    r[0][1].lo = e.e0.y;                                                                                 \
+    r[1][0].lo = e.e1.x;                                                                                 \
+    r[1][1].lo = e.e1.y;                                                                                 \
+    const ulonglong2 e2 = e.e2;                                                                          \
+    _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                      \
+        _Pragma("unroll") for (int i = 0; i < M; ++i) {                                                  \
+            mac128(r[p][0], xs[p][i].x, w[i]);                                                           \
+            mac128(r[p][1], xs[p][i].y, w[i]);                                                           \
+        }                                                                                                \
+        ulonglong2 v = make_ulonglong2(reduce128(r[p][0], m), reduce128(r[p][1], m));                    \
+        if (p == 0) {                                                                                    \
+            D0_CONST;                                                                                    \
+        }                                                                                                \
+        st2(d01 + z * 2 * ln_all + p * ln_all + o, v);                                                   \
+    }                                                                                                    \
     st2(d2 + z * ln_all + o, e2);
+// k_tensor_lin<M> and k_tensor_lin_c<M> are two compositions of the pieces, not one
+// body with a CONSTS flag: that body would be an inlined function too, and it
+// loses the same waves (the same table).
+template <int M>
+__global__ __launch_bounds__(NT) void k_tensor_lin(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
+                                                   size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorLin L,
+                                                   const Mod *mods, int logN) {
+    __shared__ u64 w[TL_MAX];
+    const Mod m = mods[blockIdx.y];
+    if ((int)threadIdx.x < M) w[threadIdx.x] = smod(L.K[threadIdx.x], L.sh[threadIdx.x], m);
+    __syncthreads();
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const size_t z = blockIdx.z, o = c.o();
+    const u64 *A = a + z * sa, *Bp = b + z * sb;
+    const Ct x = tensor_left(A, a2, sa2, z, ln_all, o, m.q), y = Ct::load(Bp, ln_all, o);
+    ulonglong2 xs[2][M];  // the summands' loads issued with the operands'
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+        for (int i = 0; i < M; ++i) xs[p][i] = ld2(L.x[i] + (2 * z + p) * L.xseg + o);
+    TENSOR_LIN_SUMS((void)0)
 }
 template <int M>
 __global__ __launch_bounds__(NT) void k_tensor_lin_c(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
                                                      size_t sa, size_t sb, const u64 *a2, size_t sa2, TensorConst C,
                                                      TensorLin L, const Mod *mods, int logN) {
     __shared__ u64 w[TL_MAX + 2];  // the summands' constants, then the left operand's and d0's
-    const size_t n = (size_t)1 << logN;
     const int l = blockIdx.y;
     const Mod m = mods[l];
     if ((int)threadIdx.x < M) w[threadIdx.x] = smod(L.K[threadIdx.x], L.sh[threadIdx.x], m);
     if (threadIdx.x == TL_MAX) w[TL_MAX] = smod(C.aK, C.ash, m);
     if (threadIdx.x == TL_MAX + 1) w[TL_MAX + 1] = C.oK ? tensor_out_const(C.oK, C.osh, m, mods, l) : 0;
     __syncthreads();
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const size_t z = blockIdx.z, o = c.o();
     const u64 *A = a + z * sa, *Bp = b + z * sb;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    if (a2) {
-        const u64 *A2 = a2 + z * sa2;
-        const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
-        a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
-        a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
-    }
-    {
-        const u64 wa = w[TL_MAX];
-        a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
-    }
-    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
+    const Ct x = add_c0(tensor_left(A, a2, sa2, z, ln_all, o, m.q), w[TL_MAX], m.q), y = Ct::load(Bp, ln_all, o);
     ulonglong2 xs[2][M];  // the summands' loads issued with the operands'
 #pragma unroll
     for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int i = 0; i < M; ++i) xs[p][i] = ld2(L.x[i] + (2 * z + p) * L.xseg + o);
-    Acc128 r[2][2];
-    r[0][0].lo = mul_barrett(a0.x, b0.x, m);
-    r[0][1].lo = mul_barrett(a0.y, b0.y, m);
-    r[1][0].lo = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    r[1][1].lo = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    ulonglong2 e2;
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            mac128(r[p][0], xs[p][i].x, w[i]);
-            mac128(r[p][1], xs[p][i].y, w[i]);
-        }
-        ulonglong2 v = make_ulonglong2(reduce128(r[p][0], m), reduce128(r[p][1], m));
-        if (p == 0) {  // read here, so it is not live across the sums
-            const u64 wo = w[TL_MAX + 1];
-            v = make_ulonglong2(add_mod(v.x, wo, m.q), add_mod(v.y, wo, m.q));
-        }
-        st2(d01 + z * 2 * ln_all + p * ln_all + o, v);
-    }
-    st2(d2 + z * ln_all + o, e2);
+    TENSOR_LIN_SUMS(v = add2(v, w[TL_MAX + 1], m.q))  // read there, so it is not live across the sums
 }
+#undef TENSOR_LIN_SUMS
 // out [2][limbs][n] = sum over members of in [members][2][limbs][n]
 __global__ __launch_bounds__(NT) void k_sum_members(u64 *out, const u64 *in, int members, size_t ln_all,
                                                     const Mod *mods, int logN) {
@@ -419,7 +494,8 @@ __global__ __launch_bounds__(NT) void k_sum_members(u64 *out, const u64 *in, int
 // arithmetic.  Output member p * members + z (column-major), each the words
 // k_tensor gives on (member z, column p).  The last group is guarded.
 constexpr int TC_MAX = 32;  // columns of one launch
-constexpr int TC_PC = 4;    // columns per thread
+constexpr int TC_PC = 4;    // columns per thread: the binding's TENSOR_COLS_PER_THREAD
+static_assert(TC_PC == TENSOR_TILE, "the record sort's column tile is the tiled tensors' tile");
 struct TensorCols {
     const u64 *b[TC_MAX];
     int P;
@@ -427,40 +503,14 @@ struct TensorCols {
 template <int PC>
 __global__ __launch_bounds__(NT) void k_tensor_cols(u64 *d01, u64 *d2, const u64 *a, size_t ln_all, size_t sa,
                                                     TensorCols C, int members, const Mod *mods, int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
-    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
-    const size_t o = (size_t)l * n + k;
-    const u64 *A = a + (size_t)z * sa;
-    const ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    ulonglong2 b0[PC], b1[PC];
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < C.P) {
-            const u64 *Bp = C.b[p0 + j];
-            b0[j] = ld2(Bp + o);
-            b1[j] = ld2(Bp + ln_all + o);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < C.P) {
-            ulonglong2 e0, e1, e2;
-            e0.x = mul_barrett(a0.x, b0[j].x, m);
-            e0.y = mul_barrett(a0.y, b0[j].y, m);
-            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
-            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
-            e2.x = mul_barrett(a1.x, b1[j].x, m);
-            e2.y = mul_barrett(a1.y, b1[j].y, m);
-            const size_t mo = (size_t)(p0 + j) * members + z;
-            st2(d01 + mo * 2 * ln_all + o, e0);
-            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
-            st2(d2 + mo * ln_all + o, e2);
-        }
-    }
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const Mod m = mods[c.l];
+    const ColTile g = col_tile<PC>(members);
+    const Ct x = Ct::load(a + (size_t)g.z * sa, ln_all, c.o());
+    tensor_tiled<PC, false>(
+        d01, d2, ln_all, c.o(), m, g.p0, C.P, [&] { return x; }, [&](int p) { return C.b[p]; },
+        [&](int p) { return (size_t)p * members + g.z; });
 }
 // out [groups][2][limbs][n] (+)= sum over the B members of each group of
 // in [groups * B][2][limbs][n] (group p = members p B .. p B + B - 1): grid
@@ -1384,12 +1434,10 @@ __global__ __launch_bounds__(NT) void k_mul_plain_sum_groups(u64 *out, const u64
 // The tie-broken differences of a chunk of comparator batches (constructRank,
 // DESIGN.md §6.3): member i of out = (a - b_i) + p_i on c0, a - b_i on c1, written
 // straight into the stack.  a is one ciphertext, so a thread loads its two pairs
-// of words once and applies them to the SAP_TM members of its tile:
+// of words once and applies them to the members of its SubTile:
 // 5 B + 2 ceil(B / TM) limb-units against the 9 B of sub_stacked followed by an
 // add_plain per member.  sub_mod then add_mod, the words of k_sub and k_c0_op.
-// A last tile narrower than SAP_TM repeats its last member and stores only the
-// valid ones.  grid: x = coefficient block, y = limb, z = member tile.
-constexpr int SAP_TM = 4;
+// grid: x = coefficient block, y = limb, z = member tile.
 struct SubAddPlainArgs {
     const u64 *b[LIN_MAX];
     const u64 *p[LIN_MAX];
@@ -1397,51 +1445,38 @@ struct SubAddPlainArgs {
 };
 __global__ __launch_bounds__(NT) void k_sub_add_plain_stacked(u64 *out, const u64 *a, SubAddPlainArgs A, size_t ln_all,
                                                               const Mod *mods, int logN) {
-    constexpr int TM = SAP_TM;
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const u64 q = mods[l].q;
-    const size_t lo = (size_t)l * n + k;
-    const int m0 = blockIdx.z * TM;
-    const ulonglong2 a0 = ld2(a + lo), a1 = ld2(a + ln_all + lo);
-    ulonglong2 b0[TM], b1[TM], p[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int m = min(m0 + t, A.B - 1);  // block-uniform
-        b0[t] = ld2(A.b[m] + lo);
-        b1[t] = ld2(A.b[m] + ln_all + lo);
-        p[t] = ld2(A.p[m] + lo);
-    }
-#pragma unroll
-    for (int t = 0; t < TM; ++t)
-        if (m0 + t < A.B) {
-            u64 *o = out + (size_t)(m0 + t) * 2 * ln_all + lo;
-            st2(o, make_ulonglong2(add_mod(sub_mod(a0.x, b0[t].x, q), p[t].x, q),
-                                   add_mod(sub_mod(a0.y, b0[t].y, q), p[t].y, q)));
-            st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
-        }
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const size_t o = c.o();
+    const u64 q = mods[c.l].q;
+    SubTile T{(int)blockIdx.z * SubTile::TM, A.B};
+    const Ct x = Ct::load(a, ln_all, o);
+    T.load(A.b, ln_all, o);
+    T.load_plain(A.p, o);
+    T.each([&](int t, int mem) {
+        add_c0(sub(x, T.b[t], q), T.p[t], q).store(out + (size_t)mem * 2 * ln_all, ln_all, o);
+    });
 }
 
 // The two-sided differences of a chunk of comparator batches (groupSums,
 // DESIGN.md §6.4): with d_i = a - b_i, member i of out = d_i + c on c0, d_i on c1,
 // and member `pm` + i = -d_i + c on c0, -d_i on c1, both written straight into
-// the stack from one load of b_i; a's two pairs of words are loaded once per tile
-// of SPM_TM members: 6 B + 2 ceil(B / TM) limb-units against the 18 B of
+// the stack from one load of b_i; a's two pairs of words are loaded once per
+// SubTile: 6 B + 2 ceil(B / TM) limb-units against the 18 B of
 // sub_stacked, negate and two add_consts.  sub_mod, sub_mod(0, .) and add_mod of
-// the constant's residue: the words of k_sub, k_neg and k_c0_op (mode 0).  A last
-// tile narrower than SPM_TM repeats its last member and stores only the valid
-// ones.  grid: x = coefficient block, y = limb, z = member tile.
-constexpr int SPM_TM = 4;
+// the constant's residue: the words of k_sub, k_neg and k_c0_op (mode 0).
+// grid: x = coefficient block, y = limb, z = member tile.
 struct SubPmConstArgs {
     const u64 *b[LIN_MAX];
     int B;
 };
+// Its body is the one it had before the shared pieces, not a composition of SubTile:
+// on SubTile its clocked time left the spread of the earlier code's own rounds
+// (profiles/kernel_bodies/kernel_clock.jsonl), so it keeps the compiled code it had.
 __global__ __launch_bounds__(NT) void k_sub_pm_const_stacked(u64 *out, const u64 *a, SubPmConstArgs A, size_t pm,
                                                              int64_t K, int sh, size_t ln_all, const Mod *mods,
                                                              int logN) {
-    constexpr int TM = SPM_TM;
+    constexpr int TM = SUB_TILE;
     const size_t n = (size_t)1 << logN;
     const int l = blockIdx.y;
     const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
@@ -1484,57 +1519,27 @@ template <int PC>
 __global__ __launch_bounds__(NT) void k_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b,
                                                      size_t ln_all, size_t sa, int P, int members, const Mod *mods,
                                                      int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
-    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
-    const size_t o = (size_t)l * n + k;
-    const u64 *A = a + (size_t)z * sa, *A2 = a2 + (size_t)z * sa;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    const ulonglong2 c0 = ld2(A2 + o), c1 = ld2(A2 + ln_all + o);
-    ulonglong2 b0[PC], b1[PC];
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < P) {
-            const u64 *Bp = b + ((size_t)(p0 + j) * members + z) * 2 * ln_all;
-            b0[j] = ld2(Bp + o);
-            b1[j] = ld2(Bp + ln_all + o);
-        }
-    }
-    a0 = make_ulonglong2(add_mod(a0.x, c0.x, m.q), add_mod(a0.y, c0.y, m.q));
-    a1 = make_ulonglong2(add_mod(a1.x, c1.x, m.q), add_mod(a1.y, c1.y, m.q));
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < P) {
-            ulonglong2 e0, e1, e2;
-            e0.x = mul_barrett(a0.x, b0[j].x, m);
-            e0.y = mul_barrett(a0.y, b0[j].y, m);
-            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
-            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
-            e2.x = mul_barrett(a1.x, b1[j].x, m);
-            e2.y = mul_barrett(a1.y, b1[j].y, m);
-            const size_t mo = (size_t)(p0 + j) * members + z;
-            st2(d01 + mo * 2 * ln_all + o, e0);
-            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
-            st2(d2 + mo * ln_all + o, e2);
-        }
-    }
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const Mod m = mods[c.l];
+    const ColTile g = col_tile<PC>(members);
+    const Ct x = Ct::load(a + (size_t)g.z * sa, ln_all, c.o()), x2 = Ct::load(a2 + (size_t)g.z * sa, ln_all, c.o());
+    tensor_tiled<PC, false>(
+        d01, d2, ln_all, c.o(), m, g.p0, P, [&] { return add(x, x2, m.q); },
+        [&](int p) { return b + ((size_t)p * members + g.z) * 2 * ln_all; },
+        [&](int p) { return (size_t)p * members + g.z; });
 }
 
 // The oriented, offset differences of a chunk of comparator batches (gatherColumns,
 // DESIGN.md §6.8): with d_z = a - b_z and K public offsets, member k * stride + z
 // of out = d_z with w_k added to c0 for an offset >= 0 and the negation of that
 // (both halves) for an offset < 0, the whole K B stack written in one pass from
-// one load of b_z; a's two pairs of words are loaded once per tile of SOF_TM
+// one load of b_z; a's two pairs of words are loaded once per SubTile of
 // batches: 2 K B + 2 B + 2 ceil(B / TM) limb-units against the (6 + 4 K + 4 K-) B
 // of sub_stacked, an add_const per offset and a negate per negative one (K- of
 // them).  sub_mod, add_mod of the constant's residue, sub_mod(0, .): the words
-// of k_sub, k_c0_op (mode 0) and k_neg.  A last tile narrower than SOF_TM repeats
-// its last batch and stores only the valid ones.
+// of k_sub, k_c0_op (mode 0) and k_neg.
 // grid: x = coefficient block, y = limb, z = batch tile.
-constexpr int SOF_TM = 4;
 constexpr int SOF_KMAX = 32;
 struct SubOffsetsArgs {
     const u64 *b[LIN_MAX];
@@ -1545,42 +1550,22 @@ struct SubOffsetsArgs {
 };
 __global__ __launch_bounds__(NT) void k_sub_offsets_stacked(u64 *out, const u64 *a, SubOffsetsArgs A, size_t stride,
                                                             size_t ln_all, const Mod *mods, int logN) {
-    constexpr int TM = SOF_TM;
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const u64 q = mods[l].q;
-    const size_t lo = (size_t)l * n + k;
-    const int m0 = blockIdx.z * TM;
-    const ulonglong2 a0 = ld2(a + lo), a1 = ld2(a + ln_all + lo);
-    ulonglong2 d0[TM], d1[TM];
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const u64 q = mods[c.l].q;
+    SubTile T{(int)blockIdx.z * SubTile::TM, A.B};
+    const Ct x = Ct::load(a, ln_all, c.o());
+    T.load(A.b, ln_all, c.o());
 #pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int m = min(m0 + t, A.B - 1);  // block-uniform
-        d0[t] = ld2(A.b[m] + lo);
-        d1[t] = ld2(A.b[m] + ln_all + lo);
-    }
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        d0[t] = make_ulonglong2(sub_mod(a0.x, d0[t].x, q), sub_mod(a0.y, d0[t].y, q));
-        d1[t] = make_ulonglong2(sub_mod(a1.x, d1[t].x, q), sub_mod(a1.y, d1[t].y, q));
-    }
+    for (int t = 0; t < SubTile::TM; ++t) T.b[t] = sub(x, T.b[t], q);  // the differences, once for all offsets
     for (int j = 0; j < A.nk; ++j) {
-        const u64 w = smod(A.K[j], A.sh[j], mods[l]);
-        const bool neg = A.neg[j] != 0;  // block-uniform
-#pragma unroll
-        for (int t = 0; t < TM; ++t)
-            if (m0 + t < A.B) {
-                ulonglong2 v0 = make_ulonglong2(add_mod(d0[t].x, w, q), add_mod(d0[t].y, w, q)), v1 = d1[t];
-                if (neg) {
-                    v0 = make_ulonglong2(sub_mod(0, v0.x, q), sub_mod(0, v0.y, q));
-                    v1 = make_ulonglong2(sub_mod(0, v1.x, q), sub_mod(0, v1.y, q));
-                }
-                u64 *o = out + ((size_t)j * stride + (size_t)(m0 + t)) * 2 * ln_all + lo;
-                st2(o, v0);
-                st2(o + ln_all, v1);
-            }
+        const u64 w = smod(A.K[j], A.sh[j], mods[c.l]);
+        const bool negate = A.neg[j] != 0;  // block-uniform
+        T.each([&](int t, int mem) {
+            Ct v = add_c0(T.b[t], w, q);
+            if (negate) v = neg(v, q);
+            v.store(out + ((size_t)j * stride + (size_t)mem) * 2 * ln_all, ln_all, c.o());
+        });
     }
 }
 
@@ -1595,43 +1580,18 @@ __global__ __launch_bounds__(NT) void k_sub_offsets_stacked(u64 *out, const u64 
 template <int KC>
 __global__ __launch_bounds__(NT) void k_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, size_t ln_all,
                                                       int P, int K, int members, const Mod *mods, int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const Mod m = mods[c.l];
     const unsigned tiles = (unsigned)(K + KC - 1) / KC;
     const int z = (int)(blockIdx.z % (unsigned)members);
     const unsigned g = blockIdx.z / (unsigned)members;
     const int k0 = (int)(g % tiles) * KC, p = (int)(g / tiles);
-    const size_t o = (size_t)l * n + k;
-    const u64 *Bp = b + ((size_t)p * members + z) * 2 * ln_all;
-    const ulonglong2 b0 = ld2(Bp + o), b1 = ld2(Bp + ln_all + o);
-    ulonglong2 a0[KC], a1[KC];
-#pragma unroll
-    for (int j = 0; j < KC; ++j) {
-        if (k0 + j < K) {
-            const u64 *Ap = a + ((size_t)(k0 + j) * members + z) * 2 * ln_all;
-            a0[j] = ld2(Ap + o);
-            a1[j] = ld2(Ap + ln_all + o);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < KC; ++j) {
-        if (k0 + j < K) {
-            ulonglong2 e0, e1, e2;
-            e0.x = mul_barrett(a0[j].x, b0.x, m);
-            e0.y = mul_barrett(a0[j].y, b0.y, m);
-            e1.x = add_mod(mul_barrett(a0[j].x, b1.x, m), mul_barrett(a1[j].x, b0.x, m), m.q);
-            e1.y = add_mod(mul_barrett(a0[j].y, b1.y, m), mul_barrett(a1[j].y, b0.y, m), m.q);
-            e2.x = mul_barrett(a1[j].x, b1.x, m);
-            e2.y = mul_barrett(a1[j].y, b1.y, m);
-            const size_t mo = ((size_t)p * K + (k0 + j)) * members + z;
-            st2(d01 + mo * 2 * ln_all + o, e0);
-            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
-            st2(d2 + mo * ln_all + o, e2);
-        }
-    }
+    const Ct y = Ct::load(b + ((size_t)p * members + z) * 2 * ln_all, ln_all, c.o());
+    tensor_tiled<KC, true>(
+        d01, d2, ln_all, c.o(), m, k0, K, [&] { return y; },
+        [&](int k) { return a + ((size_t)k * members + z) * 2 * ln_all; },
+        [&](int k) { return ((size_t)p * K + k) * members + z; });
 }
 
 // The differences of a chunk of comparator batches under L lexicographic keys
@@ -1641,14 +1601,12 @@ __global__ __launch_bounds__(NT) void k_tensor_gather(u64 *d01, u64 *d2, const u
 // (2 key + 1) count + i = d with Kn 2^shn (-eps) added to c0, both from one load of
 // b; the last key writes member 2 (L - 1) count + i = d, with p_i added to c0 when
 // the tie-break offsets are given.  a_key's two pairs of words are loaded once per
-// tile of SLX_TM operands (B = the launch's operands per key): a leading key moves
+// SubTile of operands (B = the launch's operands per key): a leading key moves
 // 6 B + 2 ceil(B / TM) limb-units against the 14 B of sub_stacked and two
 // add_consts, the last key k_sub_add_plain_stacked's 5 B + 2 ceil(B / TM) (4 B
 // without offsets).  sub_mod, then add_mod of the constant's residue or of the
-// plaintext: the words of k_sub and k_c0_op (modes 0 and 1).  A last tile narrower
-// than SLX_TM repeats its last operand and stores only the valid ones.
+// plaintext: the words of k_sub and k_c0_op (modes 0 and 1).
 // grid: x = coefficient block, y = limb, z = key * tiles + tile.
-constexpr int SLX_TM = 4;
 constexpr int SLX_KEYS = 4;
 struct SubLexArgs {
     const u64 *a[SLX_KEYS];
@@ -1658,53 +1616,29 @@ struct SubLexArgs {
 };
 __global__ __launch_bounds__(NT) void k_sub_lex_stacked(u64 *out, SubLexArgs A, size_t count, int64_t Kp, int shp,
                                                         int64_t Kn, int shn, size_t ln_all, const Mod *mods, int logN) {
-    constexpr int TM = SLX_TM;
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const u64 q = mods[l].q;
-    const size_t lo = (size_t)l * n + k;
-    const int tiles = (A.B + TM - 1) / TM;
-    const int key = (int)(blockIdx.z / (unsigned)tiles), m0 = (int)(blockIdx.z % (unsigned)tiles) * TM;  // block-uniform
-    const u64 *ap = A.a[key];
-    const ulonglong2 a0 = ld2(ap + lo), a1 = ld2(ap + ln_all + lo);
-    ulonglong2 b0[TM], b1[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const u64 *bp = A.b[key * A.B + min(m0 + t, A.B - 1)];
-        b0[t] = ld2(bp + lo);
-        b1[t] = ld2(bp + ln_all + lo);
-    }
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const u64 q = mods[c.l].q;
+    const int tiles = (A.B + SubTile::TM - 1) / SubTile::TM;
+    const int key = (int)(blockIdx.z / (unsigned)tiles);  // block-uniform
+    SubTile T{(int)(blockIdx.z % (unsigned)tiles) * SubTile::TM, A.B};
+    const Ct x = Ct::load(A.a[key], ln_all, c.o());
+    T.load(A.b + key * A.B, ln_all, c.o());
     if (key < A.L - 1) {  // a leading key: d + eps and d - eps
-        const u64 wp = smod(Kp, shp, mods[l]), wn = smod(Kn, shn, mods[l]);
-#pragma unroll
-        for (int t = 0; t < TM; ++t)
-            if (m0 + t < A.B) {
-                const u64 d0x = sub_mod(a0.x, b0[t].x, q), d0y = sub_mod(a0.y, b0[t].y, q);
-                const ulonglong2 d1 = make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q));
-                u64 *o = out + ((size_t)(2 * key) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
-                st2(o, make_ulonglong2(add_mod(d0x, wp, q), add_mod(d0y, wp, q)));
-                st2(o + ln_all, d1);
-                u64 *om = o + count * 2 * ln_all;
-                st2(om, make_ulonglong2(add_mod(d0x, wn, q), add_mod(d0y, wn, q)));
-                st2(om + ln_all, d1);
-            }
+        const u64 wp = smod(Kp, shp, mods[c.l]), wn = smod(Kn, shn, mods[c.l]);
+        T.each([&](int t, int mem) {
+            const Ct d = sub(x, T.b[t], q);
+            u64 *o = out + ((size_t)(2 * key) * count + (size_t)mem) * 2 * ln_all;
+            add_c0(d, wp, q).store(o, ln_all, c.o());
+            add_c0(d, wn, q).store(o + count * 2 * ln_all, ln_all, c.o());
+        });
     } else {  // the last key: d, with the tie-break offset when one is given
-        ulonglong2 p[TM];
-        if (A.has_p) {
-#pragma unroll
-            for (int t = 0; t < TM; ++t) p[t] = ld2(A.p[min(m0 + t, A.B - 1)] + lo);
-        }
-#pragma unroll
-        for (int t = 0; t < TM; ++t)
-            if (m0 + t < A.B) {
-                ulonglong2 d0 = make_ulonglong2(sub_mod(a0.x, b0[t].x, q), sub_mod(a0.y, b0[t].y, q));
-                if (A.has_p) d0 = make_ulonglong2(add_mod(d0.x, p[t].x, q), add_mod(d0.y, p[t].y, q));
-                u64 *o = out + ((size_t)(2 * key) * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
-                st2(o, d0);
-                st2(o + ln_all, make_ulonglong2(sub_mod(a1.x, b1[t].x, q), sub_mod(a1.y, b1[t].y, q)));
-            }
+        if (A.has_p) T.load_plain(A.p, c.o());
+        T.each([&](int t, int mem) {
+            Ct d = sub(x, T.b[t], q);
+            if (A.has_p) d = add_c0(d, T.p[t], q);
+            d.store(out + ((size_t)(2 * key) * count + (size_t)mem) * 2 * ln_all, ln_all, c.o());
+        });
     }
 }
 
@@ -1718,46 +1652,26 @@ __global__ __launch_bounds__(NT) void k_tensor_lex(u64 *d01, u64 *d2, const u64 
                                                    size_t ln_all, size_t sa, int64_t aK, int ash, const Mod *mods,
                                                    int logN) {
     __shared__ u64 wc;
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const Mod m = mods[l];
+    const Coord c = coord(logN);
+    const Mod m = mods[c.l];
     if (threadIdx.x == 0) wc = smod(aK, ash, m);
     __syncthreads();
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
-    const u64 *T = t + z * sa, *U = u + z * sa, *W = w + z * sa;
-    ulonglong2 a0 = ld2(T + o);
-    const ulonglong2 a1 = ld2(T + ln_all + o);
-    const ulonglong2 u0 = ld2(U + o), u1 = ld2(U + ln_all + o);
-    const ulonglong2 w0 = ld2(W + o), w1 = ld2(W + ln_all + o);
-    const u64 wa = wc;
-    a0 = make_ulonglong2(add_mod(a0.x, wa, m.q), add_mod(a0.y, wa, m.q));
-    const ulonglong2 b0 = make_ulonglong2(sub_mod(u0.x, w0.x, m.q), sub_mod(u0.y, w0.y, m.q));
-    const ulonglong2 b1 = make_ulonglong2(sub_mod(u1.x, w1.x, m.q), sub_mod(u1.y, w1.y, m.q));
-    ulonglong2 e0, e1, e2;
-    e0.x = mul_barrett(a0.x, b0.x, m);
-    e0.y = mul_barrett(a0.y, b0.y, m);
-    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-    st2(d01 + z * 2 * ln_all + o, e0);
-    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
-    st2(d2 + z * ln_all + o, e2);
+    if (!c.in) return;
+    const size_t z = blockIdx.z;
+    const Ct x = Ct::load(t + z * sa, ln_all, c.o()), y = Ct::load(u + z * sa, ln_all, c.o()),
+             y2 = Ct::load(w + z * sa, ln_all, c.o());
+    tensor(add_c0(x, wc, m.q), sub(y, y2, m.q), m).store(d01, d2, ln_all, z, c.o());
 }
 
 // The bounded differences of a chunk of comparator batches (runningSums,
 // DESIGN.md §6.6): for each of the NB left operands ("bounds") a_v and every b_i,
 // member v `count` + i of out = a_v - b_i with K_v 2^sh_v added to c0, written
 // straight into the stack.  Each b_i is loaded once for all bounds and every
-// a_v's two pairs of words once per tile of SBD_TM members:
+// a_v's two pairs of words once per SubTile of members:
 // (2 + 2 NB) B + 2 NB ceil(B / TM) limb-units against the 10 NB B of one sub and
 // one add_const per member and bound.  sub_mod, then add_mod of the constant's
-// residue: the words of k_sub and k_c0_op (mode 0).  A last tile narrower than
-// SBD_TM repeats its last member and stores only the valid ones.
+// residue: the words of k_sub and k_c0_op (mode 0).
 // grid: x = coefficient block, y = limb, z = member tile.
-constexpr int SBD_TM = 4;
 constexpr int SBD_NB = 2;
 struct SubBoundsArgs {
     const u64 *a[SBD_NB];
@@ -1769,41 +1683,23 @@ struct SubBoundsArgs {
 template <int NB>
 __global__ __launch_bounds__(NT) void k_sub_bounds_stacked(u64 *out, SubBoundsArgs A, size_t count, size_t ln_all,
                                                            const Mod *mods, int logN) {
-    constexpr int TM = SBD_TM;
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const u64 q = mods[l].q;
-    const size_t lo = (size_t)l * n + k;
-    const int m0 = blockIdx.z * TM;
-    ulonglong2 a0[NB], a1[NB];
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const u64 q = mods[c.l].q;
+    SubTile T{(int)blockIdx.z * SubTile::TM, A.B};
+    Ct x[NB];
 #pragma unroll
-    for (int v = 0; v < NB; ++v) {
-        a0[v] = ld2(A.a[v] + lo);
-        a1[v] = ld2(A.a[v] + ln_all + lo);
-    }
-    ulonglong2 b0[TM], b1[TM];
-#pragma unroll
-    for (int t = 0; t < TM; ++t) {
-        const int m = min(m0 + t, A.B - 1);  // block-uniform
-        b0[t] = ld2(A.b[m] + lo);
-        b1[t] = ld2(A.b[m] + ln_all + lo);
-    }
+    for (int v = 0; v < NB; ++v) x[v] = Ct::load(A.a[v], ln_all, c.o());
+    T.load(A.b, ln_all, c.o());
     u64 w[NB];
 #pragma unroll
-    for (int v = 0; v < NB; ++v) w[v] = smod(A.K[v], A.sh[v], mods[l]);
+    for (int v = 0; v < NB; ++v) w[v] = smod(A.K[v], A.sh[v], mods[c.l]);
+    T.each([&](int t, int mem) {
 #pragma unroll
-    for (int t = 0; t < TM; ++t)
-        if (m0 + t < A.B) {
-#pragma unroll
-            for (int v = 0; v < NB; ++v) {
-                u64 *o = out + ((size_t)v * count + (size_t)(m0 + t)) * 2 * ln_all + lo;
-                st2(o, make_ulonglong2(add_mod(sub_mod(a0[v].x, b0[t].x, q), w[v], q),
-                                       add_mod(sub_mod(a0[v].y, b0[t].y, q), w[v], q)));
-                st2(o + ln_all, make_ulonglong2(sub_mod(a1[v].x, b1[t].x, q), sub_mod(a1[v].y, b1[t].y, q)));
-            }
-        }
+        for (int v = 0; v < NB; ++v)
+            add_c0(sub(x[v], T.b[t], q), w[v], q)
+                .store(out + ((size_t)v * count + (size_t)mem) * 2 * ln_all, ln_all, c.o());
+    });
 }
 
 // k_tensor_pairs with the left operand of the running sums formed on load
@@ -1820,52 +1716,19 @@ template <int PC, int MODE>
 __global__ __launch_bounds__(NT) void k_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b,
                                                    size_t ln_all, size_t sa, int64_t K, int sh, int P, int members,
                                                    const Mod *mods, int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
-    const int z = (int)(blockIdx.z % (unsigned)members), p0 = (int)(blockIdx.z / (unsigned)members) * PC;
-    const size_t o = (size_t)l * n + k;
-    const u64 *A = a + (size_t)z * sa;
-    ulonglong2 a0 = ld2(A + o), a1 = ld2(A + ln_all + o);
-    ulonglong2 c0 = make_ulonglong2(0, 0), c1 = make_ulonglong2(0, 0);
-    if (MODE == 1) {
-        const u64 *W = w + (size_t)z * sa;
-        c0 = ld2(W + o);
-        c1 = ld2(W + ln_all + o);
-    }
-    ulonglong2 b0[PC], b1[PC];
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < P) {
-            const u64 *Bp = b + ((size_t)(p0 + j) * members + z) * 2 * ln_all;
-            b0[j] = ld2(Bp + o);
-            b1[j] = ld2(Bp + ln_all + o);
-        }
-    }
-    if (MODE == 0) {
-        const u64 wc = smod(K, sh, m);
-        a0 = make_ulonglong2(add_mod(a0.x, wc, m.q), add_mod(a0.y, wc, m.q));
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const Mod m = mods[c.l];
+    const ColTile g = col_tile<PC>(members);
+    const auto at = [&](int p) { return b + ((size_t)p * members + g.z) * 2 * ln_all; };
+    const auto member = [&](int p) { return (size_t)p * members + g.z; };
+    const Ct x = Ct::load(a + (size_t)g.z * sa, ln_all, c.o());
+    if constexpr (MODE == 0) {
+        tensor_tiled<PC, false>(
+            d01, d2, ln_all, c.o(), m, g.p0, P, [&] { return add_c0(x, smod(K, sh, m), m.q); }, at, member);
     } else {
-        a0 = make_ulonglong2(sub_mod(a0.x, c0.x, m.q), sub_mod(a0.y, c0.y, m.q));
-        a1 = make_ulonglong2(sub_mod(a1.x, c1.x, m.q), sub_mod(a1.y, c1.y, m.q));
-    }
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        if (p0 + j < P) {
-            ulonglong2 e0, e1, e2;
-            e0.x = mul_barrett(a0.x, b0[j].x, m);
-            e0.y = mul_barrett(a0.y, b0[j].y, m);
-            e1.x = add_mod(mul_barrett(a0.x, b1[j].x, m), mul_barrett(a1.x, b0[j].x, m), m.q);
-            e1.y = add_mod(mul_barrett(a0.y, b1[j].y, m), mul_barrett(a1.y, b0[j].y, m), m.q);
-            e2.x = mul_barrett(a1.x, b1[j].x, m);
-            e2.y = mul_barrett(a1.y, b1[j].y, m);
-            const size_t mo = (size_t)(p0 + j) * members + z;
-            st2(d01 + mo * 2 * ln_all + o, e0);
-            st2(d01 + mo * 2 * ln_all + ln_all + o, e1);
-            st2(d2 + mo * ln_all + o, e2);
-        }
+        const Ct x2 = Ct::load(w + (size_t)g.z * sa, ln_all, c.o());
+        tensor_tiled<PC, false>(d01, d2, ln_all, c.o(), m, g.p0, P, [&] { return sub(x, x2, m.q); }, at, member);
     }
 }
 
@@ -1877,15 +1740,13 @@ __global__ __launch_bounds__(NT) void k_tensor_run(u64 *d01, u64 *d2, const u64 
 // G is the order key, by `kind`: 1 writes member 2 G count + i = d with Ko 2^sho added
 // to c0 (LE / LT), 2 the same with p_i added to c0 (ROWS), 3 the two bounds
 // a_G - b + eps and a2 - b - eps as members 2 G count + i and (2 G + 1) count + i from
-// one load of b (BETWEEN).  A left operand's words are loaded once per tile of
-// SWN_TM members: a two-sided slot moves 6 B + 2 ceil(B / TM) limb-units (BETWEEN
+// one load of b (BETWEEN).  A left operand's words are loaded once per SubTile
+// of members: a two-sided slot moves 6 B + 2 ceil(B / TM) limb-units (BETWEEN
 // 6 B + 4 ceil(B / TM)) against the 14 B of sub_stacked and two add_consts, a
 // one-sided slot 4 B + 2 ceil(B / TM) (5 B with offsets) against 8 B (9 B).
 // sub_mod, then add_mod of the constant's residue or of the plaintext: the
-// words of k_sub and k_c0_op (modes 0 and 1).  A last tile narrower than SWN_TM
-// repeats its last member and stores only the valid ones.
+// words of k_sub and k_c0_op (modes 0 and 1).
 // grid: x = coefficient block, y = limb, z = slot * tiles + tile.
-constexpr int SWN_TM = 4;
 constexpr int SWN_SLOTS = 4;
 struct SubWinArgs {
     const u64 *a[SWN_SLOTS];
@@ -1894,10 +1755,13 @@ struct SubWinArgs {
     const u64 *p[LIN_MAX / 2];  // kind 2: the order key's offsets (B of them)
     int G, B, kind;
 };
+// Its body is the one it had before the shared pieces, not a composition of SubTile:
+// on SubTile its clocked time left the spread of the earlier code's own rounds
+// (profiles/kernel_bodies/kernel_clock.jsonl), so it keeps the compiled code it had.
 __global__ __launch_bounds__(NT) void k_sub_window_stacked(u64 *out, SubWinArgs A, size_t count, int64_t Kp, int shp,
                                                            int64_t Kn, int shn, int64_t Ko, int sho, size_t ln_all,
                                                            const Mod *mods, int logN) {
-    constexpr int TM = SWN_TM;
+    constexpr int TM = SUB_TILE;
     const size_t n = (size_t)1 << logN;
     const int l = blockIdx.y;
     const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
@@ -1963,31 +1827,13 @@ __global__ __launch_bounds__(NT) void k_sub_window_stacked(u64 *out, SubWinArgs 
 // and k_tensor.  u, w, u2 and w2 are stacks of one level, members at stride sa.
 __global__ __launch_bounds__(NT) void k_tensor_win(u64 *d01, u64 *d2, const u64 *u, const u64 *w, const u64 *u2,
                                                    const u64 *w2, size_t ln_all, size_t sa, const Mod *mods, int logN) {
-    const size_t n = (size_t)1 << logN;
-    const int l = blockIdx.y;
-    const size_t k = ((size_t)blockIdx.x * NT + threadIdx.x) * 2;
-    if (k >= n) return;
-    const Mod m = mods[l];
-    const size_t z = blockIdx.z, o = (size_t)l * n + k;
-    const u64 *U = u + z * sa, *W = w + z * sa, *U2 = u2 + z * sa, *W2 = w2 + z * sa;
-    const ulonglong2 u0 = ld2(U + o), u1 = ld2(U + ln_all + o);
-    const ulonglong2 w0 = ld2(W + o), w1 = ld2(W + ln_all + o);
-    const ulonglong2 x0 = ld2(U2 + o), x1 = ld2(U2 + ln_all + o);
-    const ulonglong2 y0 = ld2(W2 + o), y1 = ld2(W2 + ln_all + o);
-    const ulonglong2 a0 = make_ulonglong2(sub_mod(u0.x, w0.x, m.q), sub_mod(u0.y, w0.y, m.q));
-    const ulonglong2 a1 = make_ulonglong2(sub_mod(u1.x, w1.x, m.q), sub_mod(u1.y, w1.y, m.q));
-    const ulonglong2 b0 = make_ulonglong2(sub_mod(x0.x, y0.x, m.q), sub_mod(x0.y, y0.y, m.q));
-    const ulonglong2 b1 = make_ulonglong2(sub_mod(x1.x, y1.x, m.q), sub_mod(x1.y, y1.y, m.q));
-    ulonglong2 e0, e1, e2;
-    e0.x = mul_barrett(a0.x, b0.x, m);
-    e0.y = mul_barrett(a0.y, b0.y, m);
-    e1.x = add_mod(mul_barrett(a0.x, b1.x, m), mul_barrett(a1.x, b0.x, m), m.q);
-    e1.y = add_mod(mul_barrett(a0.y, b1.y, m), mul_barrett(a1.y, b0.y, m), m.q);
-    e2.x = mul_barrett(a1.x, b1.x, m);
-    e2.y = mul_barrett(a1.y, b1.y, m);
-    st2(d01 + z * 2 * ln_all + o, e0);
-    st2(d01 + z * 2 * ln_all + ln_all + o, e1);
-    st2(d2 + z * ln_all + o, e2);
+    const Coord c = coord(logN);
+    if (!c.in) return;
+    const Mod m = mods[c.l];
+    const size_t z = blockIdx.z;
+    const Ct x = Ct::load(u + z * sa, ln_all, c.o()), x2 = Ct::load(w + z * sa, ln_all, c.o());
+    const Ct y = Ct::load(u2 + z * sa, ln_all, c.o()), y2 = Ct::load(w2 + z * sa, ln_all, c.o());
+    tensor(sub(x, x2, m.q), sub(y, y2, m.q), m).store(d01, d2, ln_all, z, c.o());
 }
 
 // grid: x = n / NT, y = limb, z = segment
@@ -3570,7 +3416,6 @@ void ew_sum_members(u64 *out, const u64 *in, int members, int limbs, const Mod *
     const size_t ln_all = (size_t)limbs << logN;
     hipLaunchKernelGGL(k_sum_members, ew_grid(logN, limbs, 2), dim3(NT), 0, st, out, in, members, ln_all, mods, logN);
 }
-int tensor_cols_per_thread() { return TC_PC; }
 void ew_tensor_cols(u64 *d01, u64 *d2, const u64 *a, const u64 *const *cols, int P, int limbs, int members, size_t sa,
                     const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0 || P <= 0) return;
@@ -3579,11 +3424,12 @@ void ew_tensor_cols(u64 *d01, u64 *d2, const u64 *a, const u64 *const *cols, int
         TensorCols C{};
         C.P = std::min(TC_MAX, P - base);
         for (int i = 0; i < C.P; ++i) C.b[i] = cols[base + i];
-        const int groups = (C.P + TC_PC - 1) / TC_PC;
+        const int groups = (C.P + TENSOR_TILE - 1) / TENSOR_TILE;
         const double B = 8.0 * (2.0 * members * groups + 2.0 * C.P + 3.0 * C.P * members) * ln_all;
         const size_t mo = (size_t)base * members;  // first output member of this launch
-        launch_clocked(inst_name<TC_PC>("k_tensor_cols"), B, k_tensor_cols<TC_PC>, ew_grid(logN, limbs, members * groups),
-                       dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, ln_all, sa, C, members, mods, logN);
+        launch_clocked(inst_name<TENSOR_TILE>("k_tensor_cols"), B, k_tensor_cols<TENSOR_TILE>,
+                       ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a,
+                       ln_all, sa, C, members, mods, logN);
     }
 }
 void ew_sum_member_groups(u64 *out, const u64 *in, int groups, int per_group, int limbs, bool accumulate,
@@ -3810,85 +3656,95 @@ void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int
                        out, in, A, ln_all, mods, logN);
     }
 }
-int sub_add_plain_tile() { return SAP_TM; }
+namespace {
+// The launches of a stacked difference: `count` right operands per row in chunks
+// of at most per_launch.  Each launch's Args gets its B and its pointer table,
+// row-major (A.b[r * B + i] = bs[r * count + base + i], the layout of bs with
+// the chunk cut out of every row); launch(A, base, tiles) fills in the rest, books
+// the bytes and launches.
+template <typename Args, typename Launch>
+void sub_stacked_chunks(const u64 *const *bs, int rows, int count, int per_launch, Launch &&launch) {
+    for (int base = 0; base < count; base += per_launch) {
+        Args A{};
+        A.B = std::min(per_launch, count - base);
+        for (int r = 0; r < rows; ++r)
+            for (int i = 0; i < A.B; ++i) A.b[r * A.B + i] = bs[(size_t)r * count + base + i];
+        launch(A, base, (A.B + SUB_TILE - 1) / SUB_TILE);
+    }
+}
+// The launches of a tiled tensor over P columns of `members` members: grid
+// z = members * groups stays below the 65535 limit, whole column groups per
+// launch; launch(base, Pn, groups) takes columns base .. base + Pn - 1.
+template <typename Launch>
+void tensor_column_groups(int P, int members, Launch &&launch) {
+    const int per_launch = std::max(1, 65535 / members / TENSOR_TILE) * TENSOR_TILE;
+    for (int base = 0; base < P; base += per_launch) {
+        const int Pn = std::min(per_launch, P - base);
+        launch(base, Pn, (Pn + TENSOR_TILE - 1) / TENSOR_TILE);
+    }
+}
+// The launches of a member-wise tensor: at most 65535 members (grid z) each
+template <typename Launch>
+void tensor_member_chunks(int members, Launch &&launch) {
+    for (int base = 0; base < members; base += 65535) launch(base, std::min(65535, members - base));
+}
+}  // namespace
 void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, const u64 *const *ps, int members,
                               int limbs, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    for (int base = 0; base < members; base += LIN_MAX) {
-        SubAddPlainArgs A{};
-        A.B = std::min(LIN_MAX, members - base);
-        for (int i = 0; i < A.B; ++i) {
-            A.b[i] = bs[base + i];
-            A.p[i] = ps[base + i];
-        }
-        const int tiles = (A.B + SAP_TM - 1) / SAP_TM;
+    sub_stacked_chunks<SubAddPlainArgs>(bs, 1, members, LIN_MAX, [&](SubAddPlainArgs &A, int base, int tiles) {
+        for (int i = 0; i < A.B; ++i) A.p[i] = ps[base + i];
         const double B = 8.0 * (5.0 * A.B + 2.0 * tiles) * ln_all;
         launch_clocked("k_sub_add_plain_stacked", B, k_sub_add_plain_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
                        out + (size_t)base * 2 * ln_all, a, A, ln_all, mods, logN);
-    }
+    });
 }
-int sub_pm_const_tile() { return SPM_TM; }
 void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, int64_t K, int sh, int limbs,
                              const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    for (int base = 0; base < members; base += LIN_MAX) {
-        SubPmConstArgs A{};
-        A.B = std::min(LIN_MAX, members - base);
-        for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
-        const int tiles = (A.B + SPM_TM - 1) / SPM_TM;
+    sub_stacked_chunks<SubPmConstArgs>(bs, 1, members, LIN_MAX, [&](SubPmConstArgs &A, int base, int tiles) {
         const double B = 8.0 * (6.0 * A.B + 2.0 * tiles) * ln_all;
         launch_clocked("k_sub_pm_const_stacked", B, k_sub_pm_const_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
                        out + (size_t)base * 2 * ln_all, a, A, (size_t)members, K, sh, ln_all, mods, logN);
-    }
+    });
 }
-int tensor_pairs_per_thread() { return TC_PC; }
 void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
                      size_t sa, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0 || P <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    // grid z = members * groups stays below the 65535 limit: whole column groups per launch
-    const int per_launch = std::max(1, 65535 / members / TC_PC) * TC_PC;
-    for (int base = 0; base < P; base += per_launch) {
-        const int Pn = std::min(per_launch, P - base), groups = (Pn + TC_PC - 1) / TC_PC;
+    tensor_column_groups(P, members, [&](int base, int Pn, int groups) {
         const double B = 8.0 * (4.0 * members * groups + 5.0 * Pn * members) * ln_all;
         const size_t mo = (size_t)base * members;  // first column member of this launch
-        launch_clocked(inst_name<TC_PC>("k_tensor_pairs"), B, k_tensor_pairs<TC_PC>, ew_grid(logN, limbs, members * groups),
-                       dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, a2, b + mo * 2 * ln_all, ln_all, sa, Pn,
-                       members, mods, logN);
-    }
+        launch_clocked(inst_name<TENSOR_TILE>("k_tensor_pairs"), B, k_tensor_pairs<TENSOR_TILE>,
+                       ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a, a2,
+                       b + mo * 2 * ln_all, ln_all, sa, Pn, members, mods, logN);
+    });
 }
-int sub_offsets_tile() { return SOF_TM; }
 void ew_sub_offsets_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, const int64_t *Ks,
                             const int *shs, const uint8_t *negs, int noff, int limbs, const Mod *mods, int logN,
                             hipStream_t st) {
     if (limbs <= 0 || members <= 0 || noff <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
     for (int kb = 0; kb < noff; kb += SOF_KMAX)
-        for (int base = 0; base < members; base += LIN_MAX) {
-            SubOffsetsArgs A{};
-            A.B = std::min(LIN_MAX, members - base);
+        sub_stacked_chunks<SubOffsetsArgs>(bs, 1, members, LIN_MAX, [&](SubOffsetsArgs &A, int base, int tiles) {
             A.nk = std::min(SOF_KMAX, noff - kb);
-            for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
             for (int j = 0; j < A.nk; ++j) {
                 A.K[j] = Ks[kb + j];
                 A.sh[j] = (uint8_t)shs[kb + j];
                 A.neg[j] = negs[kb + j];
             }
-            const int tiles = (A.B + SOF_TM - 1) / SOF_TM;
             const double B = 8.0 * (2.0 * A.nk * A.B + 2.0 * A.B + 2.0 * tiles) * ln_all;
             launch_clocked("k_sub_offsets_stacked", B, k_sub_offsets_stacked, ew_grid(logN, limbs, tiles), dim3(NT), st,
                            out + ((size_t)kb * members + base) * 2 * ln_all, a, A, (size_t)members, ln_all, mods, logN);
-        }
+        });
 }
-constexpr int TG_KC = 4;
-int tensor_gather_per_thread() { return TG_KC; }
 void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int K, int limbs, int members,
                       const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0 || P <= 0 || K <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    const int tiles = (K + TG_KC - 1) / TG_KC;
+    const int tiles = (K + TENSOR_TILE - 1) / TENSOR_TILE;
     if ((long long)members * tiles > 65535) throw std::invalid_argument("ew_tensor_gather: too many members per column");
     // grid z = members * tiles * columns stays below the 65535 limit: whole columns per launch
     const int per_launch = std::max(1, 65535 / (members * tiles));
@@ -3896,12 +3752,11 @@ void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int 
         const int Pn = std::min(per_launch, P - base);
         const double B = 8.0 * (2.0 * members * tiles * Pn + 5.0 * Pn * K * members) * ln_all;
         const size_t mo = (size_t)base * K * members;  // first output member of this launch
-        launch_clocked(inst_name<TG_KC>("k_tensor_gather"), B, k_tensor_gather<TG_KC>,
+        launch_clocked(inst_name<TENSOR_TILE>("k_tensor_gather"), B, k_tensor_gather<TENSOR_TILE>,
                        ew_grid(logN, limbs, members * tiles * Pn), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all, a,
                        b + (size_t)base * members * 2 * ln_all, ln_all, Pn, K, members, mods, logN);
     }
 }
-int sub_lex_tile() { return SLX_TM; }
 void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *const *bs, const u64 *const *ps, int count,
                         int64_t Kp, int shp, int64_t Kn, int shn, int limbs, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || count <= 0) return;
@@ -3909,51 +3764,39 @@ void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *con
     const size_t ln_all = (size_t)limbs << logN;
     // operands of one launch: keys * B pointers in b, B in p
     const int per_launch = std::min(LIN_MAX / keys, LIN_MAX / 2);
-    for (int base = 0; base < count; base += per_launch) {
-        SubLexArgs A{};
+    sub_stacked_chunks<SubLexArgs>(bs, keys, count, per_launch, [&](SubLexArgs &A, int base, int tiles) {
         A.L = keys;
-        A.B = std::min(per_launch, count - base);
         A.has_p = ps != nullptr;
-        for (int l = 0; l < keys; ++l) {
-            A.a[l] = as[l];
-            for (int i = 0; i < A.B; ++i) A.b[l * A.B + i] = bs[(size_t)l * count + base + i];
-        }
+        for (int l = 0; l < keys; ++l) A.a[l] = as[l];
         if (ps)
             for (int i = 0; i < A.B; ++i) A.p[i] = ps[base + i];
-        const int tiles = (A.B + SLX_TM - 1) / SLX_TM;
         const double B = 8.0 * ((keys - 1) * (6.0 * A.B + 2.0 * tiles) + (ps ? 5.0 : 4.0) * A.B + 2.0 * tiles) * ln_all;
         launch_clocked("k_sub_lex_stacked", B, k_sub_lex_stacked, ew_grid(logN, limbs, keys * tiles), dim3(NT), st,
                        out + (size_t)base * 2 * ln_all, A, (size_t)count, Kp, shp, Kn, shn, ln_all, mods, logN);
-    }
+    });
 }
 void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, int limbs, int members, size_t sa,
                    int64_t aK, int ash, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    for (int base = 0; base < members; base += 65535) {  // grid z limit
-        const int cnt = std::min(65535, members - base);
+    tensor_member_chunks(members, [&](int base, int cnt) {
         const double B = 8.0 * 9.0 * cnt * ln_all;
         launch_clocked("k_tensor_lex", B, k_tensor_lex, ew_grid(logN, limbs, cnt), dim3(NT), st,
                        d01 + (size_t)base * 2 * ln_all, d2 + (size_t)base * ln_all, t + (size_t)base * sa,
                        u + (size_t)base * sa, w + (size_t)base * sa, ln_all, sa, aK, ash, mods, logN);
-    }
+    });
 }
-int sub_bounds_tile() { return SBD_TM; }
 void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64 *const *bs, int count,
                            const int64_t *Ks, const int *shs, int limbs, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || count <= 0) return;
     if (bounds < 1 || bounds > SBD_NB) throw std::invalid_argument("ew_sub_bounds_stacked: unsupported bound count");
     const size_t ln_all = (size_t)limbs << logN;
-    for (int base = 0; base < count; base += LIN_MAX) {
-        SubBoundsArgs A{};
-        A.B = std::min(LIN_MAX, count - base);
+    sub_stacked_chunks<SubBoundsArgs>(bs, 1, count, LIN_MAX, [&](SubBoundsArgs &A, int base, int tiles) {
         for (int v = 0; v < bounds; ++v) {
             A.a[v] = as[v];
             A.K[v] = Ks[v];
             A.sh[v] = shs[v];
         }
-        for (int i = 0; i < A.B; ++i) A.b[i] = bs[base + i];
-        const int tiles = (A.B + SBD_TM - 1) / SBD_TM;
         const double B = 8.0 * ((2.0 + 2.0 * bounds) * A.B + 2.0 * bounds * tiles) * ln_all;
         u64 *o = out + (size_t)base * 2 * ln_all;
         if (bounds == 1)
@@ -3962,29 +3805,25 @@ void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64
         else
             launch_clocked(inst_name<2>("k_sub_bounds_stacked"), B, k_sub_bounds_stacked<2>, ew_grid(logN, limbs, tiles),
                            dim3(NT), st, o, A, (size_t)count, ln_all, mods, logN);
-    }
+    });
 }
 void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, int P, int limbs, int members,
                    size_t sa, int64_t K, int sh, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0 || P <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    // grid z = members * groups stays below the 65535 limit: whole column groups per launch
-    const int per_launch = std::max(1, 65535 / members / TC_PC) * TC_PC;
-    for (int base = 0; base < P; base += per_launch) {
-        const int Pn = std::min(per_launch, P - base), groups = (Pn + TC_PC - 1) / TC_PC;
+    tensor_column_groups(P, members, [&](int base, int Pn, int groups) {
         const double B = 8.0 * ((w ? 4.0 : 2.0) * members * groups + 5.0 * Pn * members) * ln_all;
         const size_t mo = (size_t)base * members;  // first column member of this launch
         if (w)
-            launch_clocked(inst_name<TC_PC, 1>("k_tensor_run"), B, k_tensor_run<TC_PC, 1>,
+            launch_clocked(inst_name<TENSOR_TILE, 1>("k_tensor_run"), B, k_tensor_run<TENSOR_TILE, 1>,
                            ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all,
                            a, w, b + mo * 2 * ln_all, ln_all, sa, K, sh, Pn, members, mods, logN);
         else
-            launch_clocked(inst_name<TC_PC, 0>("k_tensor_run"), B, k_tensor_run<TC_PC, 0>,
+            launch_clocked(inst_name<TENSOR_TILE, 0>("k_tensor_run"), B, k_tensor_run<TENSOR_TILE, 0>,
                            ew_grid(logN, limbs, members * groups), dim3(NT), st, d01 + mo * 2 * ln_all, d2 + mo * ln_all,
                            a, w, b + mo * 2 * ln_all, ln_all, sa, K, sh, Pn, members, mods, logN);
-    }
+    });
 }
-int sub_window_tile() { return SWN_TM; }
 void ew_sub_window_stacked(u64 *out, const u64 *const *as, int parts, const u64 *a2, const u64 *const *bs,
                            const u64 *const *ps, int kind, int count, int64_t Kp, int shp, int64_t Kn, int shn,
                            int64_t Ko, int sho, int limbs, const Mod *mods, int logN, hipStream_t st) {
@@ -3996,38 +3835,31 @@ void ew_sub_window_stacked(u64 *out, const u64 *const *as, int parts, const u64 
     const size_t ln_all = (size_t)limbs << logN;
     // operands of one launch: slots * B pointers in b, B in p
     const int per_launch = std::min(LIN_MAX / slots, LIN_MAX / 2);
-    for (int base = 0; base < count; base += per_launch) {
-        SubWinArgs A{};
+    sub_stacked_chunks<SubWinArgs>(bs, slots, count, per_launch, [&](SubWinArgs &A, int base, int tiles) {
         A.G = parts;
-        A.B = std::min(per_launch, count - base);
         A.kind = kind;
         A.a2 = a2;
-        for (int s = 0; s < slots; ++s) {
-            A.a[s] = as[s];
-            for (int i = 0; i < A.B; ++i) A.b[s * A.B + i] = bs[(size_t)s * count + base + i];
-        }
+        for (int s = 0; s < slots; ++s) A.a[s] = as[s];
         if (ps)
             for (int i = 0; i < A.B; ++i) A.p[i] = ps[base + i];
-        const int tiles = (A.B + SWN_TM - 1) / SWN_TM;
         const double order = kind == 0   ? 0.0
                              : kind == 3 ? 6.0 * A.B + 4.0 * tiles
                                          : (kind == 2 ? 5.0 : 4.0) * A.B + 2.0 * tiles;
         const double B = 8.0 * (parts * (6.0 * A.B + 2.0 * tiles) + order) * ln_all;
         launch_clocked("k_sub_window_stacked", B, k_sub_window_stacked, ew_grid(logN, limbs, slots * tiles), dim3(NT), st,
                        out + (size_t)base * 2 * ln_all, A, (size_t)count, Kp, shp, Kn, shn, Ko, sho, ln_all, mods, logN);
-    }
+    });
 }
 void ew_tensor_win(u64 *d01, u64 *d2, const u64 *u, const u64 *w, const u64 *u2, const u64 *w2, int limbs, int members,
                    size_t sa, const Mod *mods, int logN, hipStream_t st) {
     if (limbs <= 0 || members <= 0) return;
     const size_t ln_all = (size_t)limbs << logN;
-    for (int base = 0; base < members; base += 65535) {  // grid z limit
-        const int cnt = std::min(65535, members - base);
+    tensor_member_chunks(members, [&](int base, int cnt) {
         const double B = 8.0 * 11.0 * cnt * ln_all;
         launch_clocked("k_tensor_win", B, k_tensor_win, ew_grid(logN, limbs, cnt), dim3(NT), st,
                        d01 + (size_t)base * 2 * ln_all, d2 + (size_t)base * ln_all, u + (size_t)base * sa,
                        w + (size_t)base * sa, u2 + (size_t)base * sa, w2 + (size_t)base * sa, ln_all, sa, mods, logN);
-    }
+    });
 }
 void ew_permute(u64 *out, const u64 *in, const uint32_t *perm, int limbs, int segs, Seg S, int logN,
                 hipStream_t st) {

@@ -196,6 +196,11 @@ void ew_add_scalar(u64 *out, const u64 *a, int64_t K, int limbs, int segs, Seg S
 // out[s] = a[s] * p[s]  (Barrett; S.b = 0 broadcasts one plaintext)
 void ew_mul_plain(u64 *out, const u64 *a, const u64 *p, int limbs, int segs, Seg S, const Mod *mods, int logN,
                   hipStream_t st);
+// The tiles of the kernels below that keep one operand in registers (the engine's
+// op-byte models repeat them): a tiled tensor forms its fixed operand once per
+// TENSOR_TILE tiled ones, a stacked difference loads its left operand once per
+// SUB_TILE right ones.
+constexpr int TENSOR_TILE = 4, SUB_TILE = 4;
 // per member m: d0 = a0 b0, d1 = a0 b1 + a1 b0 -> d01 [m][2][limbs][n]; d2 = a1 b1 -> d2 [m][limbs][n]
 // (a member m at m * sa, b member at m * sb; sb = 0 broadcasts one ciphertext)
 void ew_tensor(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int limbs, int members, size_t sa, size_t sb,
@@ -216,8 +221,7 @@ void ew_sum_members(u64 *out, const u64 *in, int members, int limbs, const Mod *
 // ew_tensor of a's `members` members (stride sa) against each of P single
 // ciphertexts cols[p] ([2][limbs][n]) in one pass: member p * members + z of
 // d01 / d2 holds the tensor of (member z, column p), word for word ew_tensor's.
-// a is loaded once per tensor_cols_per_thread() columns.
-int tensor_cols_per_thread();
+// a is loaded once per TENSOR_TILE columns.
 void ew_tensor_cols(u64 *d01, u64 *d2, const u64 *a, const u64 *const *cols, int P, int limbs, int members, size_t sa,
                     const Mod *mods, int logN, hipStream_t st);
 // out [groups][2][limbs][n] (+)= sum_z in [p * per_group + z] for every group p, one launch
@@ -268,33 +272,29 @@ void ew_mul_plain_sum_groups(u64 *out, const u64 *in, const u64 *const *pts, int
                              const Mod *mods, int logN, hipStream_t st);
 // Member i of out ([members][2][limbs][n]) = a - bs[i] with ps[i] added to c0
 // (a, bs[i]: [2][limbs][n], ps[i]: [limbs][n]), in one pass.  A thread applies
-// a's words to up to sub_add_plain_tile() members; word for word ew_sub, then
+// a's words to up to SUB_TILE members; word for word ew_sub, then
 // ew_c0_op mode 1, per member.
-int sub_add_plain_tile();
 void ew_sub_add_plain_stacked(u64 *out, const u64 *a, const u64 *const *bs, const u64 *const *ps, int members,
                               int limbs, const Mod *mods, int logN, hipStream_t st);
 // With d_i = a - bs[i]: member i of out ([2 members][2][limbs][n]) = d_i with
 // K 2^sh added to c0, member members + i = -d_i with K 2^sh added to c0, in one
 // pass (a, bs[i]: [2][limbs][n]).  A thread applies a's words to up to
-// sub_pm_const_tile() members; word for word ew_sub, then ew_c0_op mode 0, and
+// SUB_TILE members; word for word ew_sub, then ew_c0_op mode 0, and
 // ew_neg, then ew_c0_op mode 0, per member.
-int sub_pm_const_tile();
 void ew_sub_pm_const_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, int64_t K, int sh, int limbs,
                              const Mod *mods, int logN, hipStream_t st);
 // ew_tensor with a2 of the stacks a, a2 (`members` members at stride sa) against
 // the column-major stack b of P * members members ([2][limbs][n] each) in one
 // pass: member p * members + z of d01 / d2 holds the tensor of (a[z] + a2[z],
 // b[p * members + z]), word for word ew_tensor's.  a + a2 is formed once per
-// tensor_pairs_per_thread() columns.
-int tensor_pairs_per_thread();
+// TENSOR_TILE columns.
 void ew_tensor_pairs(u64 *d01, u64 *d2, const u64 *a, const u64 *a2, const u64 *b, int P, int limbs, int members,
                      size_t sa, const Mod *mods, int logN, hipStream_t st);
 // With d_z = a - bs[z] (a, bs[z]: [2][limbs][n]): member k * members + z of out
 // ([noff members][2][limbs][n]) = d_z with Ks[k] 2^shs[k] added to c0, negated
 // (both halves) where negs[k] is set, in one pass.  A thread loads each bs[z]
-// once for all offsets and applies a's words to up to sub_offsets_tile() batches;
+// once for all offsets and applies a's words to up to SUB_TILE batches;
 // word for word ew_sub, then ew_c0_op mode 0, then ew_neg, per member.
-int sub_offsets_tile();
 void ew_sub_offsets_stacked(u64 *out, const u64 *a, const u64 *const *bs, int members, const int64_t *Ks,
                             const int *shs, const uint8_t *negs, int noff, int limbs, const Mod *mods, int logN,
                             hipStream_t st);
@@ -302,8 +302,7 @@ void ew_sub_offsets_stacked(u64 *out, const u64 *a, const u64 *const *bs, int me
 // the column-major stack b of P * members members ([2][limbs][n] each) in one
 // pass: member (p * K + k) * members + z of d01 / d2 holds the tensor of
 // (a[k * members + z], b[p * members + z]), word for word ew_tensor's.  A column's
-// words are loaded once per tensor_gather_per_thread() members of a.
-int tensor_gather_per_thread();
+// words are loaded once per TENSOR_TILE members of a.
 void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int K, int limbs, int members,
                       const Mod *mods, int logN, hipStream_t st);
 // The stacked differences of `keys` lexicographic keys (as[key]: [2][limbs][n];
@@ -312,9 +311,8 @@ void ew_tensor_gather(u64 *d01, u64 *d2, const u64 *a, const u64 *b, int P, int 
 // out = d with Kp 2^shp added to c0 and member (2 key + 1) count + i = d with
 // Kn 2^shn added to c0 for key < keys - 1; member 2 (keys - 1) count + i = d of the
 // last key with ps[i] added to c0.  A thread applies a key's words to up to
-// sub_lex_tile() operands and loads each b once; word for word ew_sub, then
+// SUB_TILE operands and loads each b once; word for word ew_sub, then
 // ew_c0_op mode 0 / mode 1, per member.  keys <= 4.
-int sub_lex_tile();
 void ew_sub_lex_stacked(u64 *out, const u64 *const *as, int keys, const u64 *const *bs, const u64 *const *ps, int count,
                         int64_t Kp, int shp, int64_t Kn, int shn, int limbs, const Mod *mods, int logN, hipStream_t st);
 // ew_tensor of the stacks t, u, w (`members` members at stride sa, one level):
@@ -325,16 +323,15 @@ void ew_tensor_lex(u64 *d01, u64 *d2, const u64 *t, const u64 *u, const u64 *w, 
 // The bounded differences of `bounds` (1 or 2) left operands as[v] against the bs
 // (all [2][limbs][n]) in one pass: member v count + i of out ([bounds count][2][limbs][n])
 // = as[v] - bs[i] with Ks[v] 2^shs[v] added to c0.  A thread loads each bs[i] once
-// for all bounds and applies the as' words to up to sub_bounds_tile() members; word
+// for all bounds and applies the as' words to up to SUB_TILE members; word
 // for word ew_sub, then ew_c0_op mode 0, per member and bound.
-int sub_bounds_tile();
 void ew_sub_bounds_stacked(u64 *out, const u64 *const *as, int bounds, const u64 *const *bs, int count,
                            const int64_t *Ks, const int *shs, int limbs, const Mod *mods, int logN, hipStream_t st);
 // ew_tensor_pairs with the left operand formed on load: member p * members + z of
 // d01 / d2 holds the tensor of (left_z, b[p * members + z]) with left_z = a[z] with
 // K 2^sh added to c0 when w is null (ew_c0_op mode 0's words), a[z] - w[z] otherwise
 // (ew_sub's words); a and w are stacks of `members` members at stride sa.  The left
-// operand is formed once per tensor_pairs_per_thread() columns.
+// operand is formed once per TENSOR_TILE columns.
 void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, int P, int limbs, int members,
                    size_t sa, int64_t K, int sh, const Mod *mods, int logN, hipStream_t st);
 // The sign arguments of `parts` partition keys and an optional order key against
@@ -344,9 +341,8 @@ void ew_tensor_run(u64 *d01, u64 *d2, const u64 *a, const u64 *w, const u64 *b, 
 // 0 none; 1 member 2 parts count + i = as[parts] - bs[parts][i] with Ko 2^sho added to c0;
 // 2 the same with ps[i] added to c0 instead; 3 members 2 parts count + i = as[parts] - b
 // with Kp 2^shp and (2 parts + 1) count + i = a2 - b with Kn 2^shn.  A thread loads each
-// operand once and applies a left operand's words to up to sub_window_tile() members;
+// operand once and applies a left operand's words to up to SUB_TILE members;
 // word for word ew_sub, then ew_c0_op mode 0 or 1, per member.
-int sub_window_tile();
 void ew_sub_window_stacked(u64 *out, const u64 *const *as, int parts, const u64 *a2, const u64 *const *bs,
                            const u64 *const *ps, int kind, int count, int64_t Kp, int shp, int64_t Kn, int shn,
                            int64_t Ko, int sho, int limbs, const Mod *mods, int logN, hipStream_t st);

@@ -1993,7 +1993,7 @@ CtPtr Engine::mul_pairs(const Ciphertext &a, const Ciphertext &a_add, const Ciph
     }
     return product_tail(a, PB, [&](u64 *d01, u64 *d2) {
         count_bytes(5.0 * ell + ks_units(ell), PB);
-        const int per = dev::tensor_pairs_per_thread();
+        const int per = dev::TENSOR_TILE;
         count_bytes(4.0 * ell * ((Pn + per - 1) / per), B);
         dev::ew_tensor_pairs(d01, d2, a.data, a_add.data, b.data, Pn, (int)ell, B, 2 * ell * nn, MODS, LOGN, ST);
     });
@@ -2592,7 +2592,7 @@ CtPtr Engine::sub_add_plain_stacked(const Ciphertext &a0, const std::vector<cons
         pp.push_back(ps[i]->data);
     }
     dev::ew_sub_add_plain_stacked(r->data, a->data, bp.data(), pp.data(), B, (int)ell, MODS, LOGN, ST);
-    const int tile = dev::sub_add_plain_tile();
+    const int tile = dev::SUB_TILE;
     count_bytes(5.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
@@ -2631,7 +2631,7 @@ CtPtr Engine::sub_pm_const_stacked(const Ciphertext &a0, const std::vector<const
     }
     const host::SConst K = host::const_at_scale(c, a->scale);
     dev::ew_sub_pm_const_stacked(r->data, a->data, bp.data(), B, K.k, K.sh, (int)ell, MODS, LOGN, ST);
-    const int tile = dev::sub_pm_const_tile();
+    const int tile = dev::SUB_TILE;
     count_bytes(6.0 * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
@@ -2695,7 +2695,7 @@ CtPtr Engine::sub_offsets_stacked(const Ciphertext &a0, const std::vector<const 
     }
     dev::ew_sub_offsets_stacked(r->data, a->data, bp.data(), B, Ks.data(), shs.data(), negs.data(), K, (int)ell, MODS,
                                 LOGN, ST);
-    const int tile = dev::sub_offsets_tile();
+    const int tile = dev::SUB_TILE;
     count_bytes((2.0 * K + 2.0) * ell * B + 2.0 * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
@@ -2728,7 +2728,7 @@ CtPtr Engine::mul_gather(const Ciphertext &a, const Ciphertext &b, int Pn, int K
     }
     return product_tail(a, PKB, [&](u64 *d01, u64 *d2) {
         count_bytes(5.0 * ell + ks_units(ell), PKB);
-        const int per = dev::tensor_gather_per_thread();
+        const int per = dev::TENSOR_TILE;
         count_bytes(2.0 * ell * ((Kn + per - 1) / per), Pn * B);
         dev::ew_tensor_gather(d01, d2, a.data, b.data, Pn, Kn, (int)ell, B, MODS, LOGN, ST);
     });
@@ -2805,7 +2805,7 @@ CtPtr Engine::sub_lex_stacked(const std::vector<const Ciphertext *> &as, const s
     const host::SConst Kp = host::const_at_scale(eps, a0.scale), Kn = host::const_at_scale(-eps, a0.scale);
     dev::ew_sub_lex_stacked(r->data, ap.data(), L, bp.data(), pp.empty() ? nullptr : pp.data(), B, Kp.k, Kp.sh, Kn.k,
                             Kn.sh, (int)ell, MODS, LOGN, ST);
-    const int tile = dev::sub_lex_tile();
+    const int tile = dev::SUB_TILE;
     const double tiles = (double)((B + tile - 1) / tile);
     count_bytes((L - 1) * (6.0 * ell * B + 2.0 * ell * tiles) + (pp.empty() ? 4.0 : 5.0) * ell * B + 2.0 * ell * tiles, 1);
     return r;
@@ -2888,7 +2888,7 @@ CtPtr Engine::sub_bounds_stacked(const std::vector<const Ciphertext *> &as, cons
         shs[k] = K.sh;
     }
     dev::ew_sub_bounds_stacked(r->data, ap.data(), V, bp.data(), B, Ks, shs, (int)ell, MODS, LOGN, ST);
-    const int tile = dev::sub_bounds_tile();
+    const int tile = dev::SUB_TILE;
     count_bytes((2.0 + 2.0 * V) * ell * B + 2.0 * V * ell * ((B + tile - 1) / tile), 1);
     return r;
 }
@@ -2926,7 +2926,7 @@ CtPtr Engine::mul_pairs_left(const char *what, const Ciphertext &a, const Cipher
     }
     return product_tail(a, PB, [&](u64 *d01, u64 *d2) {
         count_bytes(5.0 * ell + ks_units(ell), PB);
-        const int per = dev::tensor_pairs_per_thread();
+        const int per = dev::TENSOR_TILE;
         count_bytes((w ? 4.0 : 2.0) * ell * ((Pn + per - 1) / per), B);
         const host::SConst K = w ? host::SConst{} : host::const_at_scale(c, a.scale);
         dev::ew_tensor_run(d01, d2, a.data, w ? w->data : nullptr, b.data, Pn, (int)ell, B, 2 * ell * nn, K.k, K.sh,
@@ -3030,7 +3030,7 @@ CtPtr Engine::sub_window_stacked(const std::vector<const Ciphertext *> &part_as,
     dev::ew_sub_window_stacked(r->data, ap.data(), G, kind == 3 ? ap[(size_t)G + 1] : nullptr, bp.data(),
                                pp.empty() ? nullptr : pp.data(), kind, B, Kp.k, Kp.sh, Kn.k, Kn.sh, Ko.k, Ko.sh, (int)ell,
                                MODS, LOGN, ST);
-    const int tile = dev::sub_window_tile();
+    const int tile = dev::SUB_TILE;
     const double tiles = (double)((B + tile - 1) / tile);
     const double order = kind == 0   ? 0.0
                          : kind == 3 ? 6.0 * ell * B + 4.0 * ell * tiles

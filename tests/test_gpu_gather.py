@@ -84,22 +84,31 @@ def oriented(orc, d, o):
     return orc.negate(v) if o < 0 else v
 
 
-@pytest.mark.parametrize('K', [1, 4, 5])
-@pytest.mark.parametrize('B', [1, 4, 5])
-@pytest.mark.parametrize('la', [1, 0], ids=['same-level', 'a-one-level-below'])
-def test_sub_offsets_stacked_matches_oracle(small, B, K, la):
+def _check_sub_offsets(small, B, offs, la, launches):
     orc, gpu, vals, octs, gcts = small
-    offs = OFFSETS[K]
+    K = len(offs)
     oa = orc.encrypt(vals[0], 16, la)
     with F.KernelClock(gpu) as clk:
         R = gpu.sub_offsets_stacked(gpu.from_oracle(oa), gcts[1:1 + B], offs)
-    assert clk.stats['k_sub_offsets_stacked']['launches'] == 1, sorted(clk.stats)
+    assert clk.stats['k_sub_offsets_stacked']['launches'] == launches, sorted(clk.stats)
     with pytest.raises(F.FheError):
         gpu.member(R, K * B)
     for i in range(B):
         d = orc.sub(oa, octs[1 + i])
         for k, o in enumerate(offs):
             same(gpu.member(R, k * B + i), oriented(orc, d, o))
+
+
+@pytest.mark.parametrize('K', [1, 4, 5])
+@pytest.mark.parametrize('B', [1, 4, 5])
+@pytest.mark.parametrize('la', [1, 0], ids=['same-level', 'a-one-level-below'])
+def test_sub_offsets_stacked_matches_oracle(small, B, K, la):
+    _check_sub_offsets(small, B, OFFSETS[K], la, 1)
+
+
+def test_sub_offsets_stacked_second_launch(small):
+    """33 batches under offsets of both signs: a launch takes 32, every offset's members stay 33 apart"""
+    _check_sub_offsets(small, 33, [-2, 3], 1, 2)
 
 
 @pytest.mark.parametrize('offs', [[0], [3], [-3, 0, 3]], ids=['zero', 'positive', 'mixed'])

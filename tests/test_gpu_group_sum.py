@@ -65,23 +65,32 @@ def small():
     return orc, gpu, vals
 
 
-# five members cross the guarded tail of a thread's four
-@pytest.mark.parametrize('B', [1, 4, 5])
-@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
-def test_sub_pm_const_stacked_matches_oracle(small, B, la, lb):
+def _check_sub_pm_const(small, B, la, lb, launches):
     orc, gpu, vals = small
     c = 1.0 / 16
     oa = orc.encrypt(vals[0], 16, la)
     obs = [orc.encrypt(v, 16, lb) for v in vals[1:1 + B]]
     with F.KernelClock(gpu) as clk:
         R = gpu.sub_pm_const_stacked(gpu.from_oracle(oa), [gpu.from_oracle(b) for b in obs], c)
-    assert clk.stats['k_sub_pm_const_stacked']['launches'] == 1, sorted(clk.stats)
+    assert clk.stats['k_sub_pm_const_stacked']['launches'] == launches, sorted(clk.stats)
     with pytest.raises(F.FheError):
         gpu.member(R, 2 * B)
     for i in range(B):
         d = orc.sub(oa, obs[i])
         same(gpu.member(R, i), orc.add_const(d, c))
         same(gpu.member(R, B + i), orc.add_const(orc.negate(d), c))
+
+
+# five members cross the guarded tail of a thread's four
+@pytest.mark.parametrize('B', [1, 4, 5])
+@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
+def test_sub_pm_const_stacked_matches_oracle(small, B, la, lb):
+    _check_sub_pm_const(small, B, la, lb, 1)
+
+
+def test_sub_pm_const_stacked_second_launch(small):
+    """33 members: a launch takes 32, and the second one's minus side still sits the whole 33 members on"""
+    _check_sub_pm_const(small, 33, 1, 1, 2)
 
 
 def test_sub_pm_const_stacked_with_a_above_the_operands(small):

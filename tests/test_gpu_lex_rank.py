@@ -105,6 +105,18 @@ def test_sub_lex_stacked_matches_oracle(small, la, lb, L, B, offsets):
     _check_lex_stack(orc, gpu, R, oas, obs, ops, L, B, eps)
 
 
+def test_sub_lex_stacked_second_launch(small):
+    """three keys with tie-break offsets, 11 operands: a launch holds min(32 / 3, 16) = 10, so the second
+    takes its b at key * count + base + i and its offsets at base + i"""
+    orc, gpu, vals = small
+    eps, L, B = 1.0 / 16, 3, 11
+    oas, obs, ops, gps = _lex_operands(orc, gpu, vals, L, B, 1, 1, True)
+    with F.KernelClock(gpu) as clk:
+        R = gpu.sub_lex_stacked([gpu.from_oracle(a) for a in oas], [gpu.from_oracle(b) for b in obs], eps, gps)
+    assert clk.stats['k_sub_lex_stacked']['launches'] == 2, sorted(clk.stats)
+    _check_lex_stack(orc, gpu, R, oas, obs, ops, L, B, eps)
+
+
 @pytest.mark.parametrize('offsets', [False, True], ids=['no-offsets', 'offsets'])
 @pytest.mark.parametrize('L', [2, 3])
 def test_sub_lex_stacked_with_the_keys_above_the_operands(small, L, offsets):

@@ -79,23 +79,32 @@ def small():
     return orc, gpu, vals
 
 
-# five members cross the guarded tail of a thread's four
-@pytest.mark.parametrize('B', [1, 4, 5])
-@pytest.mark.parametrize('V', [1, 2], ids=['one-bound', 'two-bounds'])
-@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
-def test_sub_bounds_stacked_matches_oracle(small, B, V, la, lb):
+def _check_sub_bounds(small, B, V, la, lb, nlaunch):
     orc, gpu, vals = small
     consts = [1.0 / 16, -1.0 / 16][:V]
     oas = [orc.encrypt(v, 16, la) for v in vals[0:V]]
     obs = [orc.encrypt(v, 16, lb) for v in vals[2:2 + B]]
     with F.KernelClock(gpu) as clk:
         Rr = gpu.sub_bounds_stacked([gpu.from_oracle(a) for a in oas], [gpu.from_oracle(b) for b in obs], consts)
-    assert launches(clk, 'k_sub_bounds_stacked') == 1, sorted(clk.stats)
+    assert launches(clk, 'k_sub_bounds_stacked') == nlaunch, sorted(clk.stats)
     with pytest.raises(F.FheError):
         gpu.member(Rr, V * B)
     for v in range(V):
         for i in range(B):
             same(gpu.member(Rr, v * B + i), orc.add_const(orc.sub(oas[v], obs[i]), consts[v]))
+
+
+# five members cross the guarded tail of a thread's four
+@pytest.mark.parametrize('B', [1, 4, 5])
+@pytest.mark.parametrize('V', [1, 2], ids=['one-bound', 'two-bounds'])
+@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
+def test_sub_bounds_stacked_matches_oracle(small, B, V, la, lb):
+    _check_sub_bounds(small, B, V, la, lb, 1)
+
+
+def test_sub_bounds_stacked_second_launch(small):
+    """33 members under two bounds: a launch takes 32, each bound's members stay 33 apart"""
+    _check_sub_bounds(small, 33, 2, 1, 1, 2)
 
 
 def test_sub_bounds_stacked_with_a_above_the_operands(small):

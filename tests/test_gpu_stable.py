@@ -46,13 +46,13 @@ def small():
     rng = np.random.default_rng(13)
     vals = [rng.uniform(-1, 1, 16) for _ in range(6)]
     pvals = [rng.uniform(-1, 1, 16) for _ in range(5)]
+    # drawn after the others, which keep their values: operands and offsets for a second launch
+    vals += [rng.uniform(-1, 1, 16) for _ in range(28)]
+    pvals += [rng.uniform(-1, 1, 16) for _ in range(28)]
     return orc, gpu, vals, pvals
 
 
-# five members cross the guarded tail of a thread's four
-@pytest.mark.parametrize('B', [1, 4, 5])
-@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
-def test_sub_add_plain_stacked_matches_oracle(small, B, la, lb):
+def _check_sub_add_plain(small, B, la, lb, launches):
     orc, gpu, vals, pvals = small
     oa = orc.encrypt(vals[0], 16, la)
     obs = [orc.encrypt(v, 16, lb) for v in vals[1:1 + B]]
@@ -60,11 +60,23 @@ def test_sub_add_plain_stacked_matches_oracle(small, B, la, lb):
     with F.KernelClock(gpu) as clk:
         R = gpu.sub_add_plain_stacked(gpu.from_oracle(oa), [gpu.from_oracle(b) for b in obs],
                                       [gpu.encode(p, 16, lev) for p in pvals[:B]])
-    assert clk.stats['k_sub_add_plain_stacked']['launches'] == 1, sorted(clk.stats)
+    assert clk.stats['k_sub_add_plain_stacked']['launches'] == launches, sorted(clk.stats)
     with pytest.raises(F.FheError):
         gpu.member(R, B)
     for i in range(B):
         same(gpu.member(R, i), orc.add_plain(orc.sub(oa, obs[i]), orc.encode(pvals[i], 16, lev)))
+
+
+# five members cross the guarded tail of a thread's four
+@pytest.mark.parametrize('B', [1, 4, 5])
+@pytest.mark.parametrize('la,lb', [(1, 1), (0, 1)], ids=['same-level', 'a-one-level-below'])
+def test_sub_add_plain_stacked_matches_oracle(small, B, la, lb):
+    _check_sub_add_plain(small, B, la, lb, 1)
+
+
+def test_sub_add_plain_stacked_second_launch(small):
+    """33 members: a launch takes 32, so member 32 comes from a second launch's table"""
+    _check_sub_add_plain(small, 33, 1, 1, 2)
 
 
 def test_sub_add_plain_stacked_with_a_above_the_operands(small):

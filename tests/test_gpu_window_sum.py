@@ -82,12 +82,12 @@ def launches(clk, name):
 # ------------------------------------------------------------ kernel level --
 @pytest.fixture(scope='module')
 def small():
-    """ring 2^12, L = 3, 40-bit scaling beside the 60-bit q0; 35 vectors, encrypted once per level on first use"""
+    """ring 2^12, L = 3, 40-bit scaling beside the 60-bit q0; 36 vectors, encrypted once per level on first use"""
     orc = O.Context(12, 3, 40, 60, 3, seed=53)
     gpu = F.Context(12, 3, 40, 60, 3, seed=53, keygen=False)
     gpu.load_keys_from(orc, [])
     rng = np.random.default_rng(19)
-    vals = [rng.uniform(-1, 1, 16) for _ in range(35)]
+    vals = [rng.uniform(-1, 1, 16) for _ in range(36)]  # the 36th: the eleventh offset of a second launch
     cache = {}
 
     def ct(i, level):
@@ -155,6 +155,18 @@ def test_sub_window_stacked_matches_oracle(small, la, lb, mode, G_, B):
         Rr = _call_window(gpu, ops, mode, eps)
     assert launches(clk, 'k_sub_window_stacked') == 1, sorted(clk.stats)
     assert not has(clk, 'k_sub_lex_stacked') and not has(clk, 'k_sub_bounds_stacked') and not has(clk, 'k_c0_op')
+    _check_window_stack(orc, gpu, Rr, ops, G_, B, mode, eps)
+
+
+@pytest.mark.parametrize('mode', [W.BETWEEN, W.ROWS], ids=['two-bounds', 'offsets'])
+def test_sub_window_stacked_second_launch(small, mode):
+    """two partition keys and an order key, 11 members: three slots put min(32 / 3, 16) = 10 in a launch"""
+    orc, gpu = small[0], small[1]
+    eps, G_, B = 1.0 / 16, 2, 11
+    ops = _window_operands(small, G_, B, mode, 1, 1)
+    with F.KernelClock(gpu) as clk:
+        Rr = _call_window(gpu, ops, mode, eps)
+    assert launches(clk, 'k_sub_window_stacked') == 2, sorted(clk.stats)
     _check_window_stack(orc, gpu, Rr, ops, G_, B, mode, eps)
 
 
